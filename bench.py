@@ -2,6 +2,7 @@
 """bench.py -- ORB extract + match throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload tum|kitti|euroc]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1], 640x480, nFeatures=1000, scale 1.2, 8 levels,
@@ -18,11 +19,16 @@ launcher did), each rank its own batch (frames are independent: no data-path
 collective), "scaling": "weak".  --workload kitti / euroc: configs[2] / configs[3]
 (benchmarks/stereo_bench.py, benchmarks/euroc_bench.py).
 
-Prints ONE JSON line on rank 0: value = frames/s of the whole job; roofline for the
-dominant kernel (HIP events on the extractor's stream; algorithmic bytes in
-DESIGN.md §5); cpu_baseline = the oracle (C restatement, -O3 -march=native) doing the
-same extract + match work on this host's cores; parity = every frame and every matched
-pair of the last batch against the oracle, plus the octree status words.
+Prints ONE JSON line on rank 0: value = frames/s of the whole job (ms_per_step = one
+timed step); roofline for the dominant kernel (HIP events on the extractor's stream,
+recorded in the timed steps themselves; algorithmic bytes in DESIGN.md §5).  A plain run
+stops there: set up, warm up, time the K steps, print.  --full adds the measurements
+and checks that take runs of their own: cpu_baseline = the oracle (C restatement, -O3
+-march=native) doing the same extract + match work on this host's cores; parity = every
+frame and every matched pair of the last batch against the oracle (a plain run reports
+the octree status words only); the host-fed and TrackLocalMap legs and, at --gpus > 1,
+the keyframe-exchange leg.  --dump-outputs DIR writes the last timed step's results
+(dump_outputs) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -382,6 +388,43 @@ def cpu_baseline(frames_np, T, sf, seconds: float, threads: int, W=640, H=480, p
                       f"matches) against the previous frame, over {n} consecutive bench frames; "
                       f"scalar port built {flags} (no OpenCV / IPP SIMD)"}
 
+DUMP_BUDGET_BYTES = 60_000_000  # every .npy of one --dump-outputs together (limit: 64 MB)
+
+
+def dump_outputs(out_dir, res: dict, match: bool) -> dict:
+    """--dump-outputs: what the timed path computed in its last step -- the arrays
+    SequencePipeline.host_results() hands a caller -- as float32 .npy files:
+      n [F]            keypoints of each frame
+      kps [F, cap, 7]  x, y, size, angle, response, octave, class_id of every keypoint
+      desc [F, cap, 32] descriptor bytes
+      mp [F, cap], nm [F]  (with matching) the previous frame's keypoint each keypoint
+                       matched (-1: none) and the matches of each pair
+      frame_index [F]  the batch indices of the frames written
+    Slots past a frame's n are never written by the kernels; they are dumped as 0 (mp: -1).
+    All B frames when they fit DUMP_BUDGET_BYTES, else a fixed (seed 0) sample of them.
+    Every value is a float32, an int below 2^24 or a byte, so float32 holds it exactly."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    n = res["n"].astype(np.int64)
+    B, cap = res["kps"].shape
+    per_frame = 4 * (cap * (7 + 32 + (1 if match else 0)) + 3)
+    keep = min(B, max(1, DUMP_BUDGET_BYTES // per_frame))
+    idx = np.arange(B) if keep == B else np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    live = np.arange(cap)[None, :] < n[idx, None]  # [F, cap]: the slots the step wrote
+    k = res["kps"][idx]
+    arrays = {"frame_index": idx.astype(np.float32), "n": n[idx].astype(np.float32),
+              "kps": np.where(live[:, :, None], np.stack([k[f].astype(np.float32) for f in k.dtype.names], -1),
+                              np.float32(0)),
+              "desc": np.where(live[:, :, None], res["desc"][idx], 0).astype(np.float32)}
+    if match:
+        arrays["mp"] = np.where(live, res["mp"][idx], -1).astype(np.float32)
+        arrays["nm"] = res["nm"][idx].astype(np.float32)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float32))
+    return {"dir": str(out_dir), "frames": int(keep), "of": int(B),
+            "bytes": int(sum(a.size * 4 for a in arrays.values())), "arrays": sorted(arrays)}
+
+
 def _match_stream(dev):
     """ORBX_MATCH_PRIO=p (tuning knob): the matcher on a torch stream of priority p over
     every CU instead of the pipeline's own stream (ORBX_MATCH_CUSTRIDE=k: on CUs 0, k,
@@ -478,7 +521,7 @@ def main():
     for flag, mod in (("--vocab", "vocab_bench"), ("--rows", "row_bench"), ("--dropin", "dropin_bench")):
         if flag in sys.argv[1:]:
             sys.path.insert(0, str(ROOT / "benchmarks"))
-            return __import__(mod).main([a for a in sys.argv[1:] if a != flag])
+            return __import__(mod).main([a for a in sys.argv[1:] if a not in (flag, "--full")])
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)  # ~60 ms timed at C1: pipeline fill/drain < 1 %
@@ -510,6 +553,12 @@ def main():
     ap.add_argument("--track-retry", type=int, default=20,
                     help="TrackWithMotionModel's second search at 2*th below this many matches (Tracking.cc:988-994; "
                          "0 = one search, for pricing it)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: the oracle parity check of the last batch, the CPU "
+                         "baseline, the host-fed and TrackLocalMap legs and (--gpus > 1) the keyframe-exchange leg; "
+                         "each still has its --no-* / --parity-frames switch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)
     args, _ = ap.parse_known_args()
 
@@ -523,6 +572,9 @@ def main():
     if args.selftest_launch:
         return selftest_launch(args, rank, world, local_rank)
     if args.workload not in ("tum", "tum5k_mono"):
+        if args.dump_outputs:
+            raise SystemExit(f"bench.py: --dump-outputs covers the headline step (--workload tum, tum5k_mono), "
+                             f"not --workload {args.workload}")
         sys.path.insert(0, str(ROOT / "benchmarks"))
         mod = {"kitti": "stereo_bench", "euroc": "euroc_bench", "tum5k": "rgbd_bench"}[args.workload]
         return __import__(mod).main([a for a in sys.argv[1:]])
@@ -637,6 +689,9 @@ def main():
 
     res = pl.host_results()
     status = pl.status()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, res, match)
     n_host = res["n"]
     mean_kps = float(n_host.mean())
     mean_matches = float(res["nm"][1:].mean()) if match and B > 1 else 0.0
@@ -659,7 +714,7 @@ def main():
                  "frac_all_lanes": round(rate * S / VALU_PEAK_GIPS, 4)}
 
     parity = {"octree_status_clean": not bool(status.any()), "basis": PARITY_BASIS}
-    if args.parity_frames != 0:
+    if args.full and args.parity_frames != 0:
         # every rank checks its own last batch (each extracts its own frames), counts summed
         from oracle import checks
         nchk = B if args.parity_frames < 0 else min(B, max(2, args.parity_frames))
@@ -677,7 +732,7 @@ def main():
     # the extraction lanes wait for their upload -- the PCIe-inclusive rate a caller whose
     # frames arrive in host memory would see.  Not `value`.
     host_fed = None
-    if match and not args.no_host_fed:
+    if args.full and match and not args.no_host_fed:
         pl.set_timing(False)
         h_frames = torch.from_numpy(frames_np).pin_memory()
         nb = len(pl.kps)
@@ -728,7 +783,7 @@ def main():
     local = None
     sf_main = pl.sf
     match_cu = None if (not match or pl._own_ms is None) else int(os.environ.get("ORBX_MATCH_CUSTRIDE", "1"))
-    if match and not args.no_local_map:
+    if args.full and match and not args.no_local_map:
         pl.close()
         del pl
         pl2 = SequencePipeline(B, W, H, lanes=args.lanes, pipelined=pipeline, device=gpu, params=prm, fx=FX,
@@ -778,7 +833,7 @@ def main():
     # received from the other ranks and its triangulation pairs against the oracle.  Not
     # `value`; the headline step itself has no collective.
     exchange = None
-    if world > 1 and not args.no_exchange:
+    if args.full and world > 1 and not args.no_exchange:
         sys.path.insert(0, str(ROOT / "benchmarks"))
         import euroc_bench
         eargs = euroc_bench.parse(["--steps", "10", "--warmup", "3", "--no-cpu-baseline"])
@@ -799,7 +854,7 @@ def main():
                                 "slabs, SearchForTriangulation against the gathered neighbours"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         threads = args.cpu_threads or min(16, len(os.sched_getaffinity(0)))
         cpu = cpu_baseline(frames_np[:32], T[:32], sf_main, args.cpu_seconds, threads, W, H, params=prm)
 
@@ -820,6 +875,8 @@ def main():
             "dtype": "u8",
             "data": "synthetic",
             "source_hash": source_hash(),
+            "full": bool(args.full),
+            "dumped_outputs": dumped,
             "config": {"workload": f"{'configs[4] extraction shape, monocular search' if c5 else 'configs[1]'}: {B} "
                                    f"synthetic 640x480 gray frames per GPU "
                                    f"(views of one textured canvas along a random walk), nFeatures={prm[0]}, scale 1.2, "

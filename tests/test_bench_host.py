@@ -279,6 +279,76 @@ def test_source_hash_tracks_the_sources():
     assert len(h) == 16 and h == bench.source_hash()
 
 
+def _fake_results(B, cap, seed=3):
+    import numpy as np
+    from orbslam2commentedbyxcm_amd import _lib as L
+    rng = np.random.default_rng(seed)
+    kps = rng.integers(0, 255, (B, cap, 28), dtype=np.uint8).view(L.KEYPOINT_DTYPE).reshape(B, cap)
+    for f in ("x", "y", "size", "angle", "response"):
+        kps[f] = rng.uniform(0, 640, (B, cap)).astype(np.float32)
+    kps["octave"] = rng.integers(0, 8, (B, cap))
+    kps["class_id"] = -1
+    n = rng.integers(0, cap + 1, B).astype(np.int32)
+    n[0], n[-1] = 0, cap
+    return {"kps": kps, "desc": rng.integers(0, 256, (B, cap, 32), dtype=np.uint8), "n": n,
+            "mp": rng.integers(-1, cap, (B, cap)).astype(np.int32), "nm": rng.integers(0, cap, B).astype(np.int32)}
+
+
+def test_dump_outputs_writes_the_step_results(tmp_path):
+    """--dump-outputs: float32 .npy files holding exactly what host_results() returned in
+    the slots the step wrote (below each frame's n), 0 (mp: -1) in the others."""
+    import numpy as np
+    B, cap = 5, 11
+    res = _fake_results(B, cap)
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 10 ** 6
+    info = bench.dump_outputs(tmp_path / "d", res, match=True)
+    got = {f.stem: np.load(f) for f in (tmp_path / "d").glob("*.npy")}
+    assert sorted(got) == ["desc", "frame_index", "kps", "mp", "n", "nm"] == info["arrays"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert info["frames"] == B and info["bytes"] == sum(a.nbytes for a in got.values())
+    assert np.array_equal(got["frame_index"], np.arange(B)) and np.array_equal(got["n"], res["n"])
+    assert np.array_equal(got["nm"], res["nm"])
+    for b in range(B):
+        n = res["n"][b]
+        for j, f in enumerate(res["kps"].dtype.names):
+            assert np.array_equal(got["kps"][b, :n, j], res["kps"][f][b, :n].astype(np.float32))
+        assert np.array_equal(got["desc"][b, :n], res["desc"][b, :n])
+        assert np.array_equal(got["mp"][b, :n], res["mp"][b, :n])
+        assert not got["kps"][b, n:].any() and not got["desc"][b, n:].any() and (got["mp"][b, n:] == -1).all()
+    info2 = bench.dump_outputs(tmp_path / "e", res, match=False)
+    assert info2["arrays"] == ["desc", "frame_index", "kps", "n"]
+
+
+def test_dump_outputs_samples_within_the_budget(tmp_path, monkeypatch):
+    """Over the byte budget a fixed sample of the frames is written: the same frames every
+    time, in batch order, and no more bytes than the budget."""
+    import numpy as np
+    B, cap = 9, 6
+    res = _fake_results(B, cap)
+    per_frame = 4 * (cap * 40 + 3)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * per_frame + 5)
+    a = bench.dump_outputs(tmp_path / "a", res, match=True)
+    b = bench.dump_outputs(tmp_path / "b", res, match=True)
+    assert a["frames"] == 4 and a["of"] == B and a["bytes"] <= bench.DUMP_BUDGET_BYTES
+    idx = np.load(tmp_path / "a" / "frame_index.npy").astype(int)
+    assert len(idx) == 4 and (np.diff(idx) > 0).all() and idx.min() >= 0 and idx.max() < B
+    for f in (tmp_path / "a").glob("*.npy"):
+        assert np.array_equal(np.load(f), np.load(tmp_path / "b" / f.name))
+    assert np.array_equal(np.load(tmp_path / "a" / "n.npy"), res["n"][idx])
+
+
+def test_plain_run_leaves_the_extra_legs_to_full():
+    """A plain run times the headline step only: every leg that takes runs of its own (oracle
+    parity, host-fed, TrackLocalMap, keyframe exchange, CPU baseline) is gated by --full."""
+    src = (ROOT / "bench.py").read_text()
+    for gate in ("if args.full and args.parity_frames != 0:", "if args.full and match and not args.no_host_fed:",
+                 "if args.full and match and not args.no_local_map:",
+                 "if args.full and world > 1 and not args.no_exchange:",
+                 "if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:"):
+        assert gate in src, gate
+    assert '"ms_per_step": round(ms_per_step, 4)' in src and "pl.run(d_frames, d_T, args.steps)" in src
+
+
 def test_exchange_leg_arguments():
     # the N-GPU headline's keyframe-exchange leg: euroc_bench.parse / run as bench.py calls them
     sys.path.insert(0, str(ROOT / "benchmarks"))

@@ -293,3 +293,47 @@ def test_sequence_pipeline_retry_below_20(oracle, orbx_built):
         else:
             assert nm[6] < 20, nm
         pl.close()
+
+
+def test_bench_plain_run_dumps_the_timed_outputs(oracle, orbx_built, tmp_path):
+    """bench.py's plain run (no --full) with --dump-outputs: one result line with the
+    headline fields and none of the legs that take runs of their own, and the dumped
+    float32 arrays are the last timed step's results -- every frame and pair of them equal
+    to the oracle's (the same check --full runs in-process), the unwritten slots blank."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    from orbslam2commentedbyxcm_amd import _lib as L
+    root = Path(__file__).resolve().parents[1]
+    B = 16
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--batch", str(B), "--dump-outputs", str(tmp_path / "dump")],
+                       capture_output=True, text=True, timeout=120, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["unit"] == "frames/s" and out["higher_is_better"] is True and out["dtype"] == "u8"
+    assert out["ms_per_step"] > 0 and abs(out["value"] - B / (out["ms_per_step"] * 1e-3)) <= 1e-3 * out["value"]
+    assert out["full"] is False and out["cpu_baseline"] is None and out["host_fed"] is None
+    assert out["with_local_map"] is None and "bit_exact" not in out["parity"]
+    d = {f.stem: np.load(f) for f in (tmp_path / "dump").glob("*.npy")}
+    assert sorted(d) == ["desc", "frame_index", "kps", "mp", "n", "nm"]
+    assert all(a.dtype == np.float32 for a in d.values()) and sum(a.nbytes for a in d.values()) <= 64 * 10 ** 6
+    assert np.array_equal(d["frame_index"], np.arange(B))
+    cap = d["kps"].shape[1]
+    kps = np.zeros((B, cap), L.KEYPOINT_DTYPE)
+    for j, f in enumerate(L.KEYPOINT_DTYPE.names):
+        kps[f] = d["kps"][:, :, j]
+    res = {"kps": kps, "desc": d["desc"].astype(np.uint8), "n": d["n"].astype(np.int32),
+           "mp": d["mp"].astype(np.int32), "nm": d["nm"].astype(np.int32)}
+    frames, off = synth.sequence(1000, B)  # bench.py's rank-0 batch
+    sf = ORBextractor(1000, 1.2, 8, 20, 7).GetScaleFactors()
+    chk = checks.check_sequence(frames, sequence_poses(off), res, sf, threads=8)
+    assert chk["bit_exact"] and chk["frames_checked"] == B and chk["pairs_checked"] == B - 1, chk
+    assert res["n"].min() > 500
+    for b in range(B):
+        n = res["n"][b]
+        assert not d["kps"][b, n:].any() and not d["desc"][b, n:].any() and (d["mp"][b, n:] == -1).all()

@@ -69,7 +69,7 @@ def test_pattern_table():
     assert list(vals[:8]) == [8, -3, 9, 5, 4, 2, 7, -12]
     assert list(vals[-4:]) == [-1, -6, 0, -11]
     assert vals.min() == -13 and vals.max() == 12
-    if REF_SRC.exists():  # only in the build container: pin the data to the reference text
+    if os.access(REF_SRC, os.R_OK):  # where the reference is readable: pin the data to its text
         import re
         text = REF_SRC.read_text(errors="replace")
         m = re.search(r"bit_pattern_31_\s*\[\s*256\s*\*\s*4\s*\]\s*=\s*\{(.*?)\};", text, re.S)
@@ -79,7 +79,7 @@ def test_pattern_table():
 
 
 def test_reference_constants():
-    if not REF_SRC.exists():
+    if not os.access(REF_SRC, os.R_OK):
         pytest.skip("reference not mounted (GPU box)")
     text = REF_SRC.read_text(errors="replace")
     assert "const int PATCH_SIZE = 31;" in text

@@ -4,7 +4,8 @@
 # usage: bash tools/gpu_job.sh TAG STEP [STEP ...]
 #   tests[=PYTEST_ARGS]   pytest -m gpu over tests/ (or the given selection / -k args)
 #   smoke                 __graft_entry__.smoke()
-#   bench=WL[,ARGS]       bench.py --workload WL (driver defaults) -> gpurun_out/TAG_WL_bench.json
+#   bench=WL[,ARGS]       bench.py --workload WL ARGS -> TAG_WL_bench.json in the output folder (the plain timed
+#                         run; bench=tum,--full adds the parity check, the CPU baseline and the other legs)
 #   prof=WL               kernel trace + FETCH/WRITE passes of the driver command (tools/prof_bench.sh)
 #   stall=WL              SQ stall / occupancy passes (tools/pmc_stall.sh)
 #   valu=WL               SQ_INSTS_* pass (tools/pmc_valu.sh)

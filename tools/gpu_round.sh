@@ -12,7 +12,8 @@ timeout -k 10 900 python -u -m pytest $SEL -m gpu -x -v --timeout 300 --timeout-
 rc=$?
 echo "pytest rc=$rc"
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 400 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
+O=${OUT:-$R/out}; mkdir -p $O  # the full line (every leg and check) -> $OUT/TAG_bench.json
+timeout -k 10 600 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 rc=$?
 echo "bench rc=$rc"
 if [ $rc -ne 0 ]; then exit $rc; fi
