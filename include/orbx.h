@@ -729,6 +729,102 @@ int orbx_vocabulary_transform_batch_device(orbx_vocabulary* voc, int batch, cons
 int orbx_vocabulary_set_timing(orbx_vocabulary* voc, int enable);
 int orbx_vocabulary_stage_times(orbx_vocabulary* voc, float* walk_ms, float* frame_ms);
 
+/* ---- KeyFrameDatabase: L1 BoW score and candidate detection (since orbx 0.2) ----
+ * KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc:31-307) with the
+ * stored keyframes' BowVectors in HBM, and the score both detections use: L1Scoring::score
+ * (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68).  Same candidates, in the same order,
+ * with the same float scores as the reference.  Only L1_NORM is built (ORB-SLAM2's
+ * vocabulary is TF_IDF / L1_NORM).  A BowVector is a pair of arrays (words ascending,
+ * values), the orbx_vocabulary_transform(_batch_device) layout.  DESIGN.md §4.14. */
+typedef struct orbx_kfdb orbx_kfdb;
+#define ORBX_KFDB_MAX_KEYFRAMES 8192 /* ceiling of max_keyframes */
+#define ORBX_KFDB_COVIS 10           /* GetBestCovisibilityKeyFrames(10) */
+
+/* L1Scoring::score(v1, v2) (ScoringObject.cpp:23-68) on two host BowVectors: the shared
+ * words in ascending order, score += fabs(vi - wi) - fabs(vi) - fabs(wi) from 0.0, then
+ * -score / 2.0 -- so two vectors without a shared word give -0.0.  Host only; needs no GPU. */
+int orbx_bow_score(const int32_t* w1, const double* v1, int n1, const int32_t* w2, const double* v2, int n2,
+                   double* score);
+
+/* KeyFrameDatabase::KeyFrameDatabase(voc) (cc:31-34) on the vocabulary's device: room for
+ * keyframe ids 0 .. max_keyframes - 1 (at most ORBX_KFDB_MAX_KEYFRAMES = 8192: one workgroup
+ * orders a query's candidates) of up to `cap` <= 8192 words each; HBM: 12 bytes x
+ * max_keyframes x cap.  A vocabulary whose scoring is not L1_NORM: ORBX_ERR_UNSUPPORTED.
+ * One database owns one stream and is not re-entrant; a call that names another stream
+ * first waits for the database's previous work. */
+int orbx_kfdb_create(const orbx_vocabulary* voc, int max_keyframes, int cap, orbx_kfdb** out);
+void orbx_kfdb_destroy(orbx_kfdb* db);
+/* max_keyframes, cap, number of stored keyframes (each nullable). */
+int orbx_kfdb_info(const orbx_kfdb* db, int* max_keyframes, int* cap, int* size);
+/* The database's hipStream_t (as void*). */
+void* orbx_kfdb_stream(orbx_kfdb* db);
+
+/* KeyFrameDatabase::add (cc:37-43) for n keyframes: keyframe ids[i] (host array; caller-chosen,
+ * in [0, max_keyframes)) stores BowVector i of d_bow_word / d_bow_value [n][src_cap], d_nbow [n]
+ * (device; the orbx_vocabulary_transform_batch_device outputs).  A database that cannot hold
+ * n more keyframes: ORBX_ERR_CAPACITY; an id that is stored already (or twice in ids):
+ * ORBX_ERR_STATE; a BowVector longer than the database's cap: ORBX_ERR_CAPACITY; nothing is
+ * stored then.  The new keyframe has an empty covisibility list and reloc_score 0.0f: the
+ * reference's mRelocScore is never initialised (KeyFrame.cc:32-64), and this is the value
+ * pinned for it.  Reads d_nbow back (synchronises the stream); the copy itself is enqueued. */
+int orbx_kfdb_add_batch_device(orbx_kfdb* db, int n, const int32_t* ids, const int32_t* d_bow_word,
+                               const double* d_bow_value, const int32_t* d_nbow, int src_cap, void* stream);
+/* The same for one keyframe from a host BowVector of n words (the drop-in add(pKF)). */
+int orbx_kfdb_add(orbx_kfdb* db, int id, const int32_t* word, const double* value, int n);
+/* KeyFrameDatabase::erase (cc:46-60): the other keyframes keep their relative order; the id
+ * may be added again and is then the newest.  An id that is not stored: ORBX_ERR_STATE. */
+int orbx_kfdb_erase(orbx_kfdb* db, int id);
+/* KeyFrameDatabase::clear (cc:63-66). */
+int orbx_kfdb_clear(orbx_kfdb* db);
+/* KeyFrame::GetBestCovisibilityKeyFrames(10) of a stored keyframe as the detections read it
+ * (cc:153, 268): n <= 10 keyframe ids (host), in the list's order.  Ids that are not stored
+ * (erased, or outside the database) never count. */
+int orbx_kfdb_set_covisibility(orbx_kfdb* db, int id, const int32_t* best, int n);
+/* mRelocScore of every id (max_keyframes floats, host; 0 for ids that are not stored):
+ * the score a relocalisation query last gave the keyframe.  Synchronous. */
+int orbx_kfdb_reloc_scores(orbx_kfdb* db, float* scores);
+
+/* float si = mpVoc->score(query, KF) (cc:133, 251) of one query BowVector (device: qcap slots,
+ * *d_qn of them used) against the stored keyframes d_ids [nids] (device) -- the minScore loop
+ * of LoopClosing.cc:119-132 in one launch.  d_score [nids] (device); NaN for an id that is
+ * not stored.  Asynchronous on `stream` (or the database's). */
+int orbx_kfdb_score_device(orbx_kfdb* db, const int32_t* d_qword, const double* d_qvalue, const int32_t* d_qn,
+                           int qcap, const int32_t* d_ids, int nids, float* d_score, void* stream);
+
+/* KeyFrameDatabase::DetectRelocalizationCandidates(F) (cc:206-307) for B query BowVectors in
+ * HBM (d_qword / d_qvalue [B][qcap], d_qn [B]; qcap <= 8192): exactly what B single calls in
+ * the order b = 0 .. B-1 give, the keyframes' persistent reloc_score included (a group sums
+ * the mRelocScore of every covisible candidate, scored by this query or left by an earlier
+ * one, cc:275-281).  Outputs (device): d_cand [B][max_cand] keyframe ids in the reference's
+ * order, d_ncand [B] the full count (only max_cand ids are written); optional diagnostics
+ * d_words [B][max_keyframes] (shared words, 0 = no candidate) and d_score [B][max_keyframes]
+ * (si, -1 = not scored), NULL = not wanted.  Asynchronous on `stream` (or the database's);
+ * after add / erase / clear / set_covisibility the first call uploads the membership and
+ * waits for that copy. */
+int orbx_kfdb_detect_relocalization_candidates_device(orbx_kfdb* db, int batch, const int32_t* d_qword,
+                                                      const double* d_qvalue, const int32_t* d_qn, int qcap,
+                                                      int32_t* d_cand, int max_cand, int32_t* d_ncand,
+                                                      int32_t* d_words, float* d_score, void* stream);
+/* KeyFrameDatabase::DetectLoopCandidates(pKF, minScore) (cc:79-195) for B independent
+ * queries: query b's GetConnectedKeyFrames() are the ids d_conn_ids[d_conn_off[b] ..
+ * d_conn_off[b+1]) (device CSR, B + 1 offsets; d_conn_ids may be NULL when every set is
+ * empty) and d_min_score [b] its minScore (device).  Outputs as above; connected keyframes
+ * report 0 words. */
+int orbx_kfdb_detect_loop_candidates_device(orbx_kfdb* db, int batch, const int32_t* d_qword, const double* d_qvalue,
+                                            const int32_t* d_qn, int qcap, const int32_t* d_conn_off,
+                                            const int32_t* d_conn_ids, const float* d_min_score, int32_t* d_cand,
+                                            int max_cand, int32_t* d_ncand, int32_t* d_words, float* d_score,
+                                            void* stream);
+/* The single-query host forms (the drop-in calls of Tracking::Relocalization, Tracking.cc:1524,
+ * and LoopClosing::DetectLoop, LoopClosing.cc:136): host BowVector of n words in, cand
+ * [max_cand] and *ncand out.  More than max_cand candidates: ORBX_ERR_CAPACITY with *ncand
+ * the count.  Synchronous. */
+int orbx_kfdb_detect_relocalization_candidates(orbx_kfdb* db, const int32_t* word, const double* value, int n,
+                                               int32_t* cand, int max_cand, int* ncand);
+int orbx_kfdb_detect_loop_candidates(orbx_kfdb* db, const int32_t* word, const double* value, int n,
+                                     const int32_t* connected, int nconnected, float min_score, int32_t* cand,
+                                     int max_cand, int* ncand);
+
 /* Alternative kernel forms and diagnostics switches, process-wide (tests and A/B tools;
  * the product reads no environment).  Names: "pz_seg" (pyramid levels per launch, 0 = one
  * launch), "pz_byte" (byte-read k_pyramid), "desc_tiles" (tile-major describe),

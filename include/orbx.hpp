@@ -1,12 +1,15 @@
-// orbx.hpp -- header-only C++ mirror of ORB_SLAM2::ORBextractor / ORBmatcher over the
-// C ABI in orbx.h (liborbx.so).  Same class names, constructor arguments, call operator,
-// getters and search entry points as include/ORBextractor.h:76-220 and
-// include/ORBmatcher.h:47-228 of the reference, with OpenCV types replaced by plain
+// orbx.hpp -- header-only C++ mirror of ORB_SLAM2::ORBextractor / ORBmatcher /
+// ORBVocabulary / KeyFrameDatabase over the C ABI in orbx.h (liborbx.so).  Same class
+// names, constructor arguments, call operator, getters and search entry points as
+// include/ORBextractor.h:76-220, include/ORBmatcher.h:47-228 and
+// include/KeyFrameDatabase.h:40-92 of the reference, with OpenCV types replaced by plain
 // containers (cv::KeyPoint == orbx_keypoint, 28 bytes; descriptor rows of 32 bytes).
 // Errors throw orbx::Error on this side of the boundary; nothing throws across it.
 #pragma once
 
 #include <cstdint>
+#include <map>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -233,5 +236,135 @@ inline void ComputeStereoFromRGBD(const orbx_camera& cam, const std::vector<orbx
     check(orbx_compute_stereo_from_rgbd(device, &cam, mvKeys.data(), n, depth, depthType, width, height, rowBytes,
                                         mDepthMapFactor, mbf, mvKeysUn.data(), mvuRight.data(), mvDepth.data()));
 }
+
+// DBoW2::BowVector (BowVector.h:59-62): word id -> value, ascending.
+typedef std::map<int32_t, double> BowVector;
+
+inline void BowArrays(const BowVector& v, std::vector<int32_t>& words, std::vector<double>& values) {
+    words.clear();
+    values.clear();
+    for (const auto& e : v) {
+        words.push_back(e.first);
+        values.push_back(e.second);
+    }
+}
+
+// L1Scoring::score(v1, v2) (DBoW2 ScoringObject.cpp:23-68); host only.
+inline double BowScore(const BowVector& v1, const BowVector& v2) {
+    std::vector<int32_t> w1, w2;
+    std::vector<double> a1, a2;
+    BowArrays(v1, w1, a1);
+    BowArrays(v2, w2, a2);
+    double s = 0.0;
+    check(orbx_bow_score(w1.data(), a1.data(), (int)w1.size(), w2.data(), a2.data(), (int)w2.size(), &s));
+    return s;
+}
+
+// ORBVocabulary (include/ORBVocabulary.h = DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>):
+// loadFromTextFile, size, transform to a BowVector, score (L1_NORM only).
+class ORBVocabulary {
+public:
+    explicit ORBVocabulary(int device = 0) : device_(device) {}
+    ~ORBVocabulary() { orbx_vocabulary_destroy(h_); }
+    ORBVocabulary(const ORBVocabulary&) = delete;
+    ORBVocabulary& operator=(const ORBVocabulary&) = delete;
+
+    bool loadFromTextFile(const std::string& filename) {
+        orbx_vocabulary_destroy(h_);
+        h_ = nullptr;
+        const int rc = orbx_vocabulary_load_text_file(filename.c_str(), device_, &h_);
+        if (rc == ORBX_ERR_ARG) return false;
+        check(rc);
+        return true;
+    }
+    unsigned int size() const {
+        int n = 0;
+        check(orbx_vocabulary_info(h_, nullptr, nullptr, nullptr, nullptr, nullptr, &n));
+        return (unsigned)n;
+    }
+    // transform(features, BowVector&, FeatureVector&, levelsup): the BowVector part
+    void transform(const uint8_t* descriptors, int n, BowVector& v, int levelsup = 4) {
+        std::vector<int32_t> bw((size_t)n + 1), fn((size_t)n + 1), fo((size_t)n + 2), fi((size_t)n + 1);
+        std::vector<double> bv((size_t)n + 1);
+        int nb = 0, nf = 0;
+        check(orbx_vocabulary_transform(h_, descriptors, n, levelsup, bw.data(), bv.data(), &nb, fn.data(), fo.data(),
+                                        fi.data(), &nf));
+        v.clear();
+        for (int i = 0; i < nb; i++) v.emplace_hint(v.end(), bw[i], bv[i]);
+    }
+    // score(v1, v2), TemplatedVocabulary.h:1198-1203
+    double score(const BowVector& v1, const BowVector& v2) const {
+        int scoring = 0;
+        check(orbx_vocabulary_info(h_, nullptr, nullptr, &scoring, nullptr, nullptr, nullptr));
+        if (scoring != 0) throw Error(ORBX_ERR_UNSUPPORTED, "orbx: only L1_NORM scoring is built");
+        return BowScore(v1, v2);
+    }
+    orbx_vocabulary* handle() const { return h_; }
+
+private:
+    orbx_vocabulary* h_ = nullptr;
+    int device_;
+};
+
+// KeyFrameDatabase (include/KeyFrameDatabase.h:40-92, src/KeyFrameDatabase.cc:31-307).  A
+// KeyFrame* is a caller-chosen id in [0, maxKeyFrames); add() takes the keyframe's mBowVec,
+// SetBestCovisibility its GetBestCovisibilityKeyFrames(10), DetectLoopCandidates its
+// GetConnectedKeyFrames().
+class KeyFrameDatabase {
+public:
+    explicit KeyFrameDatabase(const ORBVocabulary& voc, int maxKeyFrames = 4096, int maxWords = 2048)
+        : max_(maxKeyFrames) {
+        check(orbx_kfdb_create(voc.handle(), maxKeyFrames, maxWords, &h_));
+    }
+    ~KeyFrameDatabase() { orbx_kfdb_destroy(h_); }
+    KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+    KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+
+    // add(pKF): device BowVectors in the orbx_vocabulary_transform_batch_device layout
+    void add(const std::vector<int32_t>& ids, const int32_t* d_bow_word, const double* d_bow_value,
+             const int32_t* d_nbow, int src_cap, void* stream = nullptr) {
+        check(orbx_kfdb_add_batch_device(h_, (int)ids.size(), ids.data(), d_bow_word, d_bow_value, d_nbow, src_cap,
+                                         stream));
+    }
+    // add(pKF) from a host BowVector
+    void add(int id, const BowVector& bowVec) {
+        std::vector<int32_t> w;
+        std::vector<double> v;
+        BowArrays(bowVec, w, v);
+        check(orbx_kfdb_add(h_, id, w.data(), v.data(), (int)w.size()));
+    }
+    void erase(int id) { check(orbx_kfdb_erase(h_, id)); }
+    void clear() { check(orbx_kfdb_clear(h_)); }
+    void SetBestCovisibility(int id, const std::vector<int32_t>& best) {
+        check(orbx_kfdb_set_covisibility(h_, id, best.data(), (int)best.size()));
+    }
+    // vector<KeyFrame*> DetectLoopCandidates(KeyFrame* pKF, float minScore)
+    std::vector<int32_t> DetectLoopCandidates(const BowVector& bowVec, const std::set<int32_t>& connected,
+                                              float minScore) {
+        std::vector<int32_t> w, c(connected.begin(), connected.end()), out((size_t)max_);
+        std::vector<double> v;
+        BowArrays(bowVec, w, v);
+        int n = 0;
+        check(orbx_kfdb_detect_loop_candidates(h_, w.data(), v.data(), (int)w.size(), c.data(), (int)c.size(), minScore,
+                                               out.data(), max_, &n));
+        out.resize((size_t)n);
+        return out;
+    }
+    // vector<KeyFrame*> DetectRelocalizationCandidates(Frame* F)
+    std::vector<int32_t> DetectRelocalizationCandidates(const BowVector& bowVec) {
+        std::vector<int32_t> w, out((size_t)max_);
+        std::vector<double> v;
+        BowArrays(bowVec, w, v);
+        int n = 0;
+        check(orbx_kfdb_detect_relocalization_candidates(h_, w.data(), v.data(), (int)w.size(), out.data(), max_, &n));
+        out.resize((size_t)n);
+        return out;
+    }
+    orbx_kfdb* handle() { return h_; }
+
+private:
+    orbx_kfdb* h_ = nullptr;
+    int max_;
+};
 
 }  // namespace orbx

@@ -7,6 +7,7 @@ include/orbx.h (liborbx.so).  This package is the host-side mirror of the
 reference's ORBextractor / ORBmatcher interface.
 """
 from ._lib import KEYPOINT_DTYPE, OrbxError, lib  # noqa: F401
+from .database import KeyFrameDatabase  # noqa: F401
 from .extractor import ORBextractor  # noqa: F401
 
-__all__ = ["ORBextractor", "KEYPOINT_DTYPE", "OrbxError", "lib"]
+__all__ = ["ORBextractor", "KeyFrameDatabase", "KEYPOINT_DTYPE", "OrbxError", "lib"]

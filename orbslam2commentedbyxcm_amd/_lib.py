@@ -51,7 +51,11 @@ EXPORTED = [
     "orbx_search_for_triangulation_batch_device", "orbx_match_sequence_device_ex",
     "orbx_search_local_points_device", "orbx_create_mappoints_device", "orbx_update_last_frame_device",
     "orbx_extractor_last_call_us", "orbx_compute_stereo_from_rgbd", "orbx_compute_stereo_from_rgbd_device",
-    "orbx_debug_set",
+    "orbx_debug_set", "orbx_bow_score", "orbx_kfdb_create", "orbx_kfdb_destroy", "orbx_kfdb_info", "orbx_kfdb_stream",
+    "orbx_kfdb_add_batch_device", "orbx_kfdb_add", "orbx_kfdb_erase", "orbx_kfdb_clear", "orbx_kfdb_set_covisibility",
+    "orbx_kfdb_reloc_scores", "orbx_kfdb_score_device", "orbx_kfdb_detect_relocalization_candidates_device",
+    "orbx_kfdb_detect_loop_candidates_device", "orbx_kfdb_detect_relocalization_candidates",
+    "orbx_kfdb_detect_loop_candidates",
 ]
 
 ORBX_DEPTH_U16 = 0
@@ -275,6 +279,26 @@ def lib() -> C.CDLL:
     L.orbx_vocabulary_set_timing.argtypes = [vp, C.c_int]
     L.orbx_vocabulary_stage_times.argtypes = [vp, fp, fp]
     L.orbx_debug_set.argtypes = [C.c_char_p, C.c_int]
+    L.orbx_bow_score.argtypes = [i32p, dp, C.c_int, i32p, dp, C.c_int, dp]
+    L.orbx_kfdb_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
+    L.orbx_kfdb_destroy.argtypes = [vp]
+    L.orbx_kfdb_destroy.restype = None
+    L.orbx_kfdb_info.argtypes = [vp, ip, ip, ip]
+    L.orbx_kfdb_stream.argtypes = [vp]
+    L.orbx_kfdb_stream.restype = vp
+    L.orbx_kfdb_add_batch_device.argtypes = [vp, C.c_int, i32p, vp, vp, vp, C.c_int, vp]
+    L.orbx_kfdb_add.argtypes = [vp, C.c_int, i32p, dp, C.c_int]
+    L.orbx_kfdb_erase.argtypes = [vp, C.c_int]
+    L.orbx_kfdb_clear.argtypes = [vp]
+    L.orbx_kfdb_set_covisibility.argtypes = [vp, C.c_int, i32p, C.c_int]
+    L.orbx_kfdb_reloc_scores.argtypes = [vp, fp]
+    L.orbx_kfdb_score_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp]
+    L.orbx_kfdb_detect_relocalization_candidates_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp,
+                                                                    vp, vp, vp]
+    L.orbx_kfdb_detect_loop_candidates_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int,
+                                                          vp, vp, vp, vp]
+    L.orbx_kfdb_detect_relocalization_candidates.argtypes = [vp, i32p, dp, C.c_int, i32p, C.c_int, ip]
+    L.orbx_kfdb_detect_loop_candidates.argtypes = [vp, i32p, dp, C.c_int, i32p, C.c_int, C.c_float, i32p, C.c_int, ip]
     L.orbx_version.restype = C.c_char_p
     L.orbx_device_count.argtypes = [ip]
     L.orbx_last_error.restype = C.c_char_p

@@ -354,7 +354,7 @@ int orbx::extractor_pyramid(orbx_extractor* ex, PyrView* v, bool allow_l0) {
 
 extern "C" {
 
-const char* orbx_version(void) { return "orbx 0.1 (gfx950)"; }
+const char* orbx_version(void) { return "orbx 0.2 (gfx950)"; }
 
 
 int orbx_device_count(int* n) {

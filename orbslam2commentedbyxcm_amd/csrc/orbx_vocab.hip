@@ -288,6 +288,11 @@ struct orbx_vocabulary {
     long long ncalls = 0;
 };
 
+namespace orbx {
+// the HIP device a vocabulary lives on (orbx_kfdb.hip: a KeyFrameDatabase shares it)
+int vocabulary_device(const orbx_vocabulary* v) { return v->device; }
+}  // namespace orbx
+
 namespace {
 
 int fail(int code, const char* what) {

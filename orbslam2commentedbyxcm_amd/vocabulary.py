@@ -101,6 +101,16 @@ class ORBVocabulary:
     def stream(self) -> int:
         return L.lib().orbx_vocabulary_stream(self._h)
 
+    def score(self, v1, v2) -> float:
+        """TemplatedVocabulary::score(v1, v2) (TemplatedVocabulary.h:1198-1203) for the
+        L1_NORM scoring object (ScoringObject.cpp:23-68); BowVectors as dicts or (words,
+        values) arrays.  The other scoring codes are not built: ORBX_ERR_UNSUPPORTED."""
+        from .database import bow_score
+
+        if self.getScoringType() != L1_NORM:
+            raise L.OrbxError(L.ORBX_ERR_UNSUPPORTED, "only L1_NORM scoring is built")
+        return bow_score(v1, v2)
+
     # -- transform ----------------------------------------------------------------
     def transform_features(self, desc: np.ndarray, levelsup: int = 0):
         """Per-descriptor transform(feature, word_id, weight, nid, levelsup): returns
