@@ -23,6 +23,7 @@
 
 #include "orbx_gmem.h"
 #include "orbx_kernels.h"
+#include "orbx_rot_hist.h"
 
 namespace orbx {
 
@@ -90,43 +91,6 @@ __device__ __forceinline__ int hamming(const Desc& x, const uint8_t* p) {
     return __popcll(x.a ^ a.x) + __popcll(x.b ^ a.y) + __popcll(x.c ^ b.x) + __popcll(x.d ^ b.y);
 }
 
-// rotHist bin of a match (ORBmatcher.cc:363-371)
-__device__ __forceinline__ int rot_bin(float a1, float a2) {
-    const float factor = kHistoLength / 360.0f;
-    float rot = a1 - a2;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == kHistoLength) bin = 0;
-    return bin;
-}
-
-// ComputeThreeMaxima, ORBmatcher.cc:1935-1977, on LDS bin counts (one thread).
-__device__ void three_maxima(const int* h, int* ind) {
-    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-    for (int i = 0; i < kHistoLength; i++) {
-        const int s = h[i];
-        if (s > max1) {
-            max3 = max2; max2 = max1; max1 = s;
-            ind3 = ind2; ind2 = ind1; ind1 = i;
-        } else if (s > max2) {
-            max3 = max2; max2 = s;
-            ind3 = ind2; ind2 = i;
-        } else if (s > max3) {
-            max3 = s;
-            ind3 = i;
-        }
-    }
-    if (max2 < 0.1f * (float)max1) {
-        ind2 = -1;
-        ind3 = -1;
-    } else if (max3 < 0.1f * (float)max1) {
-        ind3 = -1;
-    }
-    ind[0] = ind1;
-    ind[1] = ind2;
-    ind[2] = ind3;
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------ SearchByBoW
@@ -134,7 +98,7 @@ __device__ void three_maxima(const int* h, int* ind) {
 __global__ __launch_bounds__(kBowThreads) void k_bow(const BowProblem* __restrict__ probs) {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ int s_hist[kHistoLength];
-    __shared__ int s_ind[3];
+    __shared__ RotMaxima s_rm;
     __shared__ int s_nrec;
     const BowProblem pb = probs[blockIdx.x];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -199,12 +163,11 @@ __global__ __launch_bounds__(kBowThreads) void k_bow(const BowProblem* __restric
     }
     if (!pb.check_ori) return;
     __syncthreads();
-    if (tid == 0) three_maxima(s_hist, s_ind);
+    if (tid == 0) s_rm = three_maxima(s_hist);
     __syncthreads();
     const int nrec = s_nrec;
     for (int r = tid; r < nrec; r += kBowThreads) {
-        const int b = bins[r];
-        if (b != s_ind[0] && b != s_ind[1] && b != s_ind[2]) pb.matches[items[r]] = -1;
+        if (!s_rm.keeps(bins[r])) pb.matches[items[r]] = -1;
     }
 }
 
@@ -329,7 +292,7 @@ __global__ __launch_bounds__(kInitScanThreads) void k_init_scan(const InitProble
 __global__ __launch_bounds__(kBowThreads) void k_init(const InitProblem* __restrict__ probs, int lists_lds) {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ int s_hist[kHistoLength];
-    __shared__ int s_ind[3];
+    __shared__ RotMaxima s_rm;
     __shared__ int s_nrec;
     const InitProblem pb = probs[blockIdx.x];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -480,14 +443,13 @@ __global__ __launch_bounds__(kBowThreads) void k_init(const InitProblem* __restr
         }
         if (lane == 0) s_nrec = nrec;
         wave_lds_fence();
-        if (pb.check_ori && lane == 0) three_maxima(s_hist, s_ind);
+        if (pb.check_ori && lane == 0) s_rm = three_maxima(s_hist);
     }
     __syncthreads();
     if (pb.check_ori) {
         const int nrec = s_nrec;
         for (int r = tid; r < nrec; r += kBowThreads) {
-            const int b = bins[r];
-            if (b != s_ind[0] && b != s_ind[1] && b != s_ind[2]) m12[items[r]] = -1;
+            if (!s_rm.keeps(bins[r])) m12[items[r]] = -1;
         }
         __syncthreads();
     }

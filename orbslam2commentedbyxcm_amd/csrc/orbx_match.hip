@@ -16,6 +16,7 @@
 #include "orbx_gmem.h"
 #include "orbx_error.h"
 #include "orbx_kernels.h"
+#include "orbx_rot_hist.h"
 
 namespace orbx {
 
@@ -189,14 +190,11 @@ constexpr int kNumCells = kGridCols * kGridRows;
 // per octave of its range, the buckets of the blocks its rows touch, and drops the rows
 // of the two end blocks outside the window (iy % kRowBlk in the entry).  Octaves >= noct share
 // the last bucket (the host sets noct above every keypoint's octave).
-#ifndef ORBX_ROWBLK_LOG2
 // 4-row blocks (round 3): the end blocks of a small window carry fewer rows outside it.
 // Scoring alone configs[4] 707 -> 659 us, configs[1] 71.7 -> 66.8 us; 2-row blocks
 // 639 / 66.1 us but a slower sort and no pipelined gain (configs[4] 92.6-94.8k against
 // 95.4-95.8k frames/s for 4 rows, 93.9-95.4k for 8)
-#define ORBX_ROWBLK_LOG2 2
-#endif
-constexpr int kRowBlkLog2 = ORBX_ROWBLK_LOG2;
+constexpr int kRowBlkLog2 = 2;
 constexpr int kRowBlk = 1 << kRowBlkLog2;     // grid rows per bucket block
 constexpr int kNumBlk = kGridRows / kRowBlk;  // 6
 static_assert(kGridRows % kRowBlk == 0 && kRowBlk <= 8, "row blocks tile the grid; 3 row bits in an orun entry");
@@ -307,21 +305,15 @@ __device__ void build_octave_runs(const unsigned* skey, const uint16_t* colstart
 constexpr int kProjThreads = 1024;      // default workgroup size of k_proj_search
 constexpr int kProjThreadsSmall = 256;  // small-footprint variant (overlapped with other work)
 constexpr int kProjThreadsTiny = 64;    // one wave per problem (a background stream's footprint)
-#ifndef ORBX_SPLIT_SCORE_THREADS
-#define ORBX_SPLIT_SCORE_THREADS 1024
-#endif
 // the sequence matcher's scoring workgroup (r05w: 512 threads within noise at configs[1],
 // configs[4] 113.6-115.4k -> 106.1-107.0k frames/s)
-constexpr int kSplitScoreThreads = ORBX_SPLIT_SCORE_THREADS;
+constexpr int kSplitScoreThreads = 1024;
 constexpr int kTopK = ORBX_TOPK;
-#ifndef ORBX_LANE_TOPK
-#define ORBX_LANE_TOPK 6
-#endif
 // candidates each scoring lane keeps before the group merge.  A lane that saw more and
 // runs dry truncates the query's list (a re-scoring on the replay's critical path later):
 // 6 measured configs[4] 81.5k frames/s against 77.0k for 4 and 81.0k for 8, configs[1]
 // unchanged (profiles/r02_n_lane_topk_ab.log)
-constexpr int kLaneTopK = ORBX_LANE_TOPK;           // candidate-list length per query
+constexpr int kLaneTopK = 6;
 // The sequence matcher's split scoring kernel runs beside the extraction lanes, where its
 // registers are what counts (4 waves a SIMD: every VGPR it holds is 4 the extraction's waves
 // on that SIMD cannot have).  Without the next-query prefetch it holds 83 VGPRs instead of
@@ -329,13 +321,7 @@ constexpr int kLaneTopK = ORBX_LANE_TOPK;           // candidate-list length per
 // -> 90.6-91.0k frames/s (lists of 4; 3 and 5 measured 89.8k and 89.3-89.6k), configs[1]
 // 228.0-228.8k -> 229.4-230.0k (profiles/r06_scoring_registers_ab.txt).  The single calls
 // keep both (their latency is the query loads').
-#ifndef ORBX_SPLIT_LANE_TOPK
-#define ORBX_SPLIT_LANE_TOPK 4
-#endif
-#ifndef ORBX_SPLIT_PREFETCH
-#define ORBX_SPLIT_PREFETCH 0
-#endif
-constexpr int kSplitLaneTopK = ORBX_SPLIT_LANE_TOPK;
+constexpr int kSplitLaneTopK = 4;
 // Lanes per query of the split scoring (0: by window width, 4 / 8 / 16 as the other forms).
 // Two: the balance counters (-DORBX_SCORE_COUNT) showed a 16-lane group's busiest lane with
 // twice its mean work and the wave's with 2.5 times, which smaller groups cut; a pair
@@ -343,16 +329,11 @@ constexpr int kSplitLaneTopK = ORBX_SPLIT_LANE_TOPK;
 // width) -> 94.0-94.2k frames/s; one lane (lists of 12) 84.6-84.8k, four 91.5-91.6k; lists of
 // 4 / 5 / 8 for the pair 90.5-90.7k / 91.0-91.5k / 93.1-93.6k against 93.1-93.6k for 6;
 // configs[1] 228.9-230.0k -> 230.8-232.5k (profiles/r06_scoring_registers_ab.txt).
-#ifndef ORBX_SPLIT_KR_ALL
-#define ORBX_SPLIT_KR_ALL 2
-#endif
-constexpr int kSplitKr = ORBX_SPLIT_KR_ALL;
-#ifndef ORBX_SPLIT_KR2_TOPK
-#define ORBX_SPLIT_KR2_TOPK 6
-#endif
+constexpr int kSplitKr = 2;
+constexpr int kSplitKr2TopK = 6;  // a pair's lanes keep lists of 6 (above)
 // a lane's list length in a KR-lane group of the split scoring: a lone lane keeps the whole list
 __host__ __device__ constexpr int split_lane_topk(int kr) {
-    return kr == 1 ? kTopK : kr == 2 ? ORBX_SPLIT_KR2_TOPK : kSplitLaneTopK;
+    return kr == 1 ? kTopK : kr == 2 ? kSplitKr2TopK : kSplitLaneTopK;
 }
 static_assert(kTopK % 4 == 0, "lists are stored as uint4s");
 constexpr int kListVec = kTopK / 4;        // uint4s per stored list
@@ -443,9 +424,6 @@ __device__ __forceinline__ QueryReg shfl_query(const QueryReg& x, int src) {
     return r;
 }
 
-#ifndef ORBX_MED3_INSERT
-#define ORBX_MED3_INSERT 1
-#endif
 // v_med3_u32 (no integer builtin; max(a, min(b, c)) is not matched to it)
 __device__ __forceinline__ unsigned med3_u32(unsigned a, unsigned b, unsigned c) {
     unsigned d;
@@ -455,19 +433,12 @@ __device__ __forceinline__ unsigned med3_u32(unsigned a, unsigned b, unsigned c)
 // Insert key into the ascending list k[0..L) (keys distinct), dropping the largest.  With
 // k[i-1] <= k[i] the new k[i] is max(k[i-1], min(key, k[i])) = med3(k[i-1], key, k[i]):
 // one instruction per entry, top down, branch-free (a key above k[L-1] changes nothing).
+// (The compare-and-select form under a `key < k[L-1]` branch was the alternative.)
 template <int L>
 __device__ __forceinline__ void sorted_insert(unsigned (&k)[L], unsigned key) {
-#if ORBX_MED3_INSERT
 #pragma unroll
     for (int i = L - 1; i > 0; i--) k[i] = med3_u32(k[i - 1], key, k[i]);
     k[0] = key < k[0] ? key : k[0];
-#else
-    if (key < k[L - 1]) {  // top down (reads k[i-1] first)
-#pragma unroll
-        for (int i = L - 1; i > 0; i--) k[i] = key < k[i - 1] ? k[i - 1] : (key < k[i] ? key : k[i]);
-        k[0] = key < k[0] ? key : k[0];
-    }
-#endif
 }
 
 // The kTopK best candidates of a query (GetFeaturesInArea + the overload's filters)
@@ -482,18 +453,9 @@ __device__ __forceinline__ void sorted_insert(unsigned (&k)[L], unsigned key) {
 // row (out = kNoEntry).  Must be called with the whole wave active.
 // K = 64: one query per wave, all lanes over its window (the replay's re-scoring of a
 // query whose list ran out, a single query on the critical path).
-#ifndef ORBX_SCORE_KR_FIXED
-#define ORBX_SCORE_KR_FIXED 0
-#endif
-#ifndef ORBX_VISIT_RCP
-#define ORBX_VISIT_RCP 1
-#endif
-#ifndef ORBX_SCORE_PAIR
-// two bucket entries per scan step with descriptors from global memory (round 3): the
-// configs[4] matcher alone 1.114 -> 1.047 ms, the drop-in rows a11-a14 1-3 % faster,
-// pipelined steps unchanged (within noise)
-#define ORBX_SCORE_PAIR 1
-#endif
+// With descriptors from global memory the scan takes two bucket entries per step (round 3):
+// the configs[4] matcher alone 1.114 -> 1.047 ms, the drop-in rows a11-a14 1-3 % faster,
+// pipelined steps unchanged (within noise).
 template <int K, int KL = kLaneTopK>
 __device__ void score_groupk(const ProjProblem& pb, const ProjParams& P, const QueryReg& QR, bool valid,
                              const SortedGrid& G, const int* sfmp, unsigned out[kTopK]) {
@@ -544,18 +506,12 @@ __device__ void score_groupk(const ProjProblem& pb, const ProjParams& P, const Q
             int sh = 0;
             while (sh < kLog2K && (nv << (sh + 1)) <= K) sh++;
             const int lpc = 1 << sh, sub = r & (lpc - 1);
-#if ORBX_VISIT_RCP
             // v / nor without an integer division (~25 VALU): (v + 0.5) / nor lies at least
             // 0.5 / nor >= 1/64 from an integer (nor <= 32, v < 2^11), far above the error of
             // v_rcp_f32 and one multiply
             const float inv_nor = __builtin_amdgcn_rcpf((float)max(nor, 1));
-#endif
             for (int v = r >> sh; v < nv; v += K >> sh) {
-#if ORBX_VISIT_RCP
                 const int cq = (int)(((float)v + 0.5f) * inv_nor);
-#else
-                const int cq = v / nor;
-#endif
                 const int ix = cr.x0 + cq, o = blo + (v - cq * nor);
                 {
                     // the rows y0..y1 of this column and octave: blocks b0..b1, whose
@@ -565,7 +521,6 @@ __device__ void score_groupk(const ProjProblem& pb, const ProjParams& P, const Q
 #if ORBX_SCORE_COUNT
                     n_pair++;
 #endif
-#if ORBX_SCORE_PAIR
                     if (!G.sdesc) {
                         // two entries per step (a and a + lpc): their LDS chains (entry,
                         // position, key) and descriptor loads are independent, so they overlap
@@ -614,7 +569,7 @@ __device__ void score_groupk(const ProjProblem& pb, const ProjParams& P, const Q
                         }
                         continue;
                     }
-#endif
+                    // descriptors in sorted order (G.sdesc): one entry per step
                     for (int a = s0 + sub; a < e1; a += lpc) {
                         const int ent = G.orun[a];
                         const int p = ent & 0x1fff, yr = ent >> 13;
@@ -624,29 +579,15 @@ __device__ void score_groupk(const ProjProblem& pb, const ProjParams& P, const Q
                         const float disty = kp.y - Q.v;
                         if (!(fabsf(distx) < Q.r && fabsf(disty) < Q.r)) continue;
                         if (sfmp && claim_blocks(sfmp[p])) continue;  // null: nothing claimed yet
-                        int d;
-                        if (G.sdesc) {
-                            if (Q.er_max >= 0.f && pb.u_right) {
-                                const float ur = ldg(pb.u_right + sk_idx(G.skey[p]));
-                                if (ur > 0 && fabsf(Q.ur - ur) > Q.er_max) continue;
-                            }
-                            const uint4 a4 = G.sdesc[2 * p], b4 = G.sdesc[2 * p + 1];
-                            d = __popcll(q0 ^ ((unsigned long long)a4.y << 32 | a4.x)) +
-                                __popcll(q1 ^ ((unsigned long long)a4.w << 32 | a4.z)) +
-                                __popcll(q2 ^ ((unsigned long long)b4.y << 32 | b4.x)) +
-                                __popcll(q3 ^ ((unsigned long long)b4.w << 32 | b4.z));
-                        } else {
-                            const unsigned kk = G.skey[p];
-                            if (kk & kKeyBlocked) continue;
-                            const int i = sk_idx(kk);
-                            if (Q.er_max >= 0.f && pb.u_right) {
-                                const float ur = ldg(pb.u_right + i);
-                                if (ur > 0 && fabsf(Q.ur - ur) > Q.er_max) continue;
-                            }
-                            const ulonglong2* tt = (const ulonglong2*)(pb.desc + (size_t)i * 32);
-                            const ulonglong2 t0 = ldg(tt), t1 = ldg(tt + 1);
-                            d = __popcll(q0 ^ t0.x) + __popcll(q1 ^ t0.y) + __popcll(q2 ^ t1.x) + __popcll(q3 ^ t1.y);
+                        if (Q.er_max >= 0.f && pb.u_right) {
+                            const float ur = ldg(pb.u_right + sk_idx(G.skey[p]));
+                            if (ur > 0 && fabsf(Q.ur - ur) > Q.er_max) continue;
                         }
+                        const uint4 a4 = G.sdesc[2 * p], b4 = G.sdesc[2 * p + 1];
+                        const int d = __popcll(q0 ^ ((unsigned long long)a4.y << 32 | a4.x)) +
+                                      __popcll(q1 ^ ((unsigned long long)a4.w << 32 | a4.z)) +
+                                      __popcll(q2 ^ ((unsigned long long)b4.y << 32 | b4.x)) +
+                                      __popcll(q3 ^ ((unsigned long long)b4.w << 32 | b4.z));
                         const unsigned key = ((unsigned)d << 13) | (unsigned)p;
                         seen++;
                         sorted_insert<KL>(k, key);
@@ -714,13 +655,7 @@ __device__ __forceinline__ void score_rowk(const ProjProblem& pb, const ProjPara
     score_groupk<kScoreRow>(pb, P, QR, valid, G, sfmp, out);
 }
 
-#ifndef ORBX_SPLIT_PERSIST
-#define ORBX_SPLIT_PERSIST 1
-#endif
-#ifndef ORBX_PERSIST_BATCH
-#define ORBX_PERSIST_BATCH 32
-#endif
-// The split scoring's lane pairs without lockstep between pairs (ORBX_SPLIT_PERSIST): a pair
+// The split scoring's lane pairs without lockstep between pairs: a pair
 // walks its query's visits and scans as score_groupk<2> does, and when both its lanes are
 // through it merges, writes the list and takes the workgroup's next query from an LDS
 // counter.  In lockstep a wave's 32 pairs wait for the busiest on every query (1.4 times
@@ -728,7 +663,7 @@ __device__ __forceinline__ void score_rowk(const ProjProblem& pb, const ProjPara
 // scan step of every lane with work.  Merges, list writes and query loads run for
 // kPersistBatch lanes at a time (or when no lane is left scanning), so that block runs once
 // per several queries.  Same lists as score_groupk<2>.
-constexpr int kPersistBatch = ORBX_PERSIST_BATCH;
+constexpr int kPersistBatch = 32;
 __device__ void score_pairs(const ProjProblem& pb, const ProjParams& P, const SortedGrid& G, uint4* qk, int* qmp,
                             float* qang, int* s_next) {
     constexpr int KL = split_lane_topk(2);
@@ -955,26 +890,21 @@ __device__ void grid_sort(const ProjProblem& pb, unsigned* skey, unsigned* cnt) 
     __syncthreads();
 }
 
-// ORBX_SPLIT_SXY_GLOBAL=1: the sequence matcher's scoring form keeps the sorted keypoint
-// positions in its grid record in global memory (where k_seq_commit reads them) instead
-// of LDS -- 8 B per keypoint (40 KB at configs[4]) less LDS held beside the extraction
-// lanes.  Measured slower (r05r: configs[4] 106.6-108.5k -> 103.8-104.8k frames/s): the
-// scoring's own window reads cost more than the LDS frees.
-#ifndef ORBX_SPLIT_SXY_GLOBAL
-#define ORBX_SPLIT_SXY_GLOBAL 0
-#endif
-constexpr bool kSplitSxyGlobal = ORBX_SPLIT_SXY_GLOBAL != 0;
-
 // LDS layout of k_proj_search (byte offsets), shared by the kernel and its launcher.
+// The sorted keypoint positions stay in LDS in every form.  The sequence matcher's scoring
+// form was tried with them in its grid record in global memory (where k_seq_commit reads
+// them) instead -- 8 B per keypoint (40 KB at configs[4]) less LDS held beside the
+// extraction lanes -- and measured slower (r05r: configs[4] 106.6-108.5k -> 103.8-104.8k
+// frames/s): the scoring's own window reads cost more than the LDS frees.
 struct ProjLds {
     size_t skey, colstart, bstart, orun, sxy, sfmp, owner, sang, elist, sdesc, qk, qmp, qang, mlist, mbin, total;
-    __host__ __device__ ProjLds(int n, int nq, bool dlds, bool qlds, int noct, bool replay = true, bool xy = true) {
+    __host__ __device__ ProjLds(int n, int nq, bool dlds, bool qlds, int noct, bool replay = true) {
         skey = 0;
         colstart = align16((size_t)n * 4);
         bstart = align16(colstart + (size_t)(kGridCols + 1) * 2);
         orun = align16(bstart + (size_t)bucket_table_len(noct) * 2);
         sxy = align16(orun + (size_t)n * 2);
-        sfmp = sxy + (xy ? (size_t)n * 8 : 0);  // !xy: the positions live in global memory
+        sfmp = sxy + (size_t)n * 8;
         // the claims and the replay's owner map (neither without the replay: the split
         // scoring keeps a keypoint's initial claim as bit 31 of its sorted key)
         owner = sfmp + (replay ? (size_t)n * 4 : 0);
@@ -998,17 +928,239 @@ struct ProjLds {
     }
 };
 
-// Wave 0's sequential replay (H5) of one problem over the per-query candidate lists qk
-// (kTopK entries per query) built by the scoring phase: every query takes the first still
-// unclaimed entries of its list (claims only ever block more keypoints, so these are its
-// exact best / second best while the list has them), resolved 64 queries at a time as a
-// fixpoint (below); a query whose list ran out is re-scored against the current claims;
-// then the rotation histogram (ORBmatcher.cc:1750-1786, 1935-1977).  sfmp / owner: the
-// claims and the owner map by sorted position (LDS, owner initialised to 0x7fffffff);
-// elist: kTopK x 64 words of LDS; angle_of(p): the angle of the keypoint at sorted
-// position p.  Whole wave active.  (The previous form committed the chunk's prefix
-// before its first conflict per round: configs[4] 447 rounds and 796 us per problem
-// against 191 iterations and 445 us for this one, configs[1] 73 -> 59 us.)
+// ---- the sequential replay (H5): what its one-wave and workgroup forms share
+//
+// Every query takes the first still unclaimed entries of its candidate list (claims only
+// ever block more keypoints, so these are its exact best / second best while the list has
+// them), resolved a chunk of queries at a time as a fixpoint (ReplayList); a query whose
+// list ran out is re-scored against the current claims (replay_rescore); then the rotation
+// histogram (replay_rot_check).
+
+// The next chunk's lists, MapPoints and queries (the latter for a re-scoring), loaded
+// while the chunk before it replays.  Unconditional loads (a clamped index; ok marks the
+// real ones): a load under a per-lane branch makes the compiler merge its registers at the
+// join, which waits for the data at once and turns the prefetch into a stall.
+struct ReplayPrefetch {
+    uint4 l[kListVec];
+    int mp = -1;
+    QueryReg q;
+    bool ok = false;
+    __device__ __forceinline__ void fetch(const ProjProblem& pb, const uint4* qk, const int* qmp, int qn) {
+        const int qc = min(qn, pb.nq - 1);  // nq >= 1 wherever fetch runs
+        ok = qn < pb.nq;
+        q = load_query(pb, qc);
+        mp = qmp[qc];
+#pragma unroll
+        for (int v = 0; v < kListVec; v++) l[v] = qk[kListVec * qc + v];
+    }
+};
+
+// One thread's query of the current chunk: its list and its choice.  S: the stride of the
+// lists in LDS (elist[j * S + thread]: an entry is picked by a per-thread index,
+// conflict-free), the chunk's width.  The methods take the search's parameters P and lastp
+// (the last sorted position, which clamps an absent entry's owner-map slot) instead of the
+// struct holding them: held, they measured 1-2 % slower on the single-call rows a11-a14.
+//
+// Fixpoint form.  The reference's loop is a function of the query order: query l's
+// choice (first two unclaimed entries, acceptance) depends only on the claims of the
+// queries before it.  Within a chunk every thread evaluates its choice against the
+// committed claims plus the current proposals of the earlier threads (an LDS owner map:
+// owner[p] = lowest thread proposing p), and all threads re-evaluate together until no
+// thread changes (Jacobi iteration: after t iterations the first t threads are final, so
+// it converges, and its fixpoint is the sequential result).  A chunk with k independent
+// conflicts then costs one iteration plus the longest dependency chain, not k rounds.  A
+// thread whose list ran out stops the commit (it is re-scored against the committed
+// claims); a thread accepting a MapPoint whose claim does not block (a11: Observations()
+// == 0) does not -- later threads ignore its proposal, and the commit keeps the last claim
+// of a keypoint.
+template <int S>
+struct ReplayList {
+    unsigned* const el;  // this thread's column of elist
+    int mp = -1;
+    unsigned e[kTopK];
+    // Derived once per list (at the chunk's start and after a re-scoring): its entries'
+    // owner-map slots, vm = the real entries (bits), full = it may hide unlisted
+    // candidates, lastgt = its last real entry is beyond the acceptance threshold.
+    int oa[kTopK];
+    unsigned vm = 0;
+    bool full = false, lastgt = false;
+    // this thread's claims block later queries (a11: only a MapPoint with observations)
+    bool bself = false;
+    // bit j: entry j is taken by a committed claim
+    unsigned cblk = 0;
+    // the choice (eval): c1 = the best free entry, acc = it is accepted, exh = the list
+    // ran out (exhausted: unlisted candidates may be the answer)
+    unsigned c1 = kNoEntry;
+    bool exh = false, acc = false;
+
+    __device__ __forceinline__ ReplayList(unsigned* elist, int thread) : el(elist + thread) {}
+
+    // the prefetched query becomes this thread's (no query: an empty list)
+    __device__ __forceinline__ void load(const ReplayPrefetch& nx) {
+        mp = nx.ok ? nx.mp : -1;
+#pragma unroll
+        for (int v = 0; v < kListVec; v++) {
+            e[4 * v] = mp >= 0 ? nx.l[v].x : kNoEntry;
+            e[4 * v + 1] = mp >= 0 ? nx.l[v].y : kNoEntry;
+            e[4 * v + 2] = mp >= 0 ? nx.l[v].z : kNoEntry;
+            e[4 * v + 3] = mp >= 0 ? nx.l[v].w : kNoEntry;
+        }
+    }
+    __device__ __forceinline__ void set_list(const ProjParams& P, int lastp) {
+        vm = 0;
+        int lastd = -1;
+#pragma unroll
+        for (int j = 0; j < kTopK; j++) {
+            el[j * S] = e[j];
+            oa[j] = min(ent_pos(e[j]), lastp);
+            vm |= (e[j] < kTrunc ? 1u : 0u) << j;
+            if (e[j] < kTrunc) lastd = ent_dist(e[j]);
+        }
+        full = e[kTopK - 1] != kNoEntry;
+        lastgt = lastd > P.accept_th;
+    }
+    // The chunk's start: the list, the claims before the chunk (cblk: one batch of
+    // independent LDS reads, and Observations() loads for a11) and the first choice.
+    __device__ __forceinline__ void start(const ProjParams& P, int lastp, const int* sfmp) {
+        set_list(P, lastp);
+        bself = false;
+        cblk = 0;
+        if (mp >= 0) {
+            bself = claim_blocks(mp);
+#pragma unroll
+            for (int j = 0; j < kTopK; j++) cblk |= (claim_blocks(sfmp[oa[j]]) ? 1u : 0u) << j;
+        }
+        c1 = kNoEntry;
+        exh = acc = false;
+        if (mp >= 0) eval(P, cblk);
+    }
+    // A re-scored list holds free keypoints only.  (In the one-wave form the re-scored
+    // lane f is also the first active lane: no earlier proposals.)
+    __device__ __forceinline__ void relist(const ProjParams& P, int lastp) {
+        cblk = 0;
+        set_list(P, lastp);
+        eval(P, 0);
+    }
+    // The choice given the blocked entries bm.  Bit arithmetic on the free mask; c1 / c2
+    // read from elist.
+    __device__ __forceinline__ void eval(const ProjParams& P, unsigned bm) {
+        const int need = P.ratio_mode ? 2 : 1;
+        const unsigned fm = vm & ~bm;
+        const int cnt = __popc(fm);
+        const unsigned a1 = fm ? el[__builtin_ctz(fm) * S] : kNoEntry;
+        // a full (or truncated) list may hide unlisted candidates -- but they are at
+        // least as far as its last exact entry (the list holds the smallest keys), so
+        // when that entry, or the free c1 of a ratio test, is already beyond the
+        // acceptance threshold the query stays unmatched
+        bool x = full && cnt < need;
+        if (x && ((cnt == 0 && lastgt) || (cnt == 1 && ent_dist(a1) > P.accept_th))) x = false;
+        bool a = !x && fm != 0 && ent_dist(a1) <= P.accept_th;
+        if (a && P.ratio_mode) {
+            const unsigned f2 = fm & (fm - 1);
+            const unsigned a2 = f2 ? el[__builtin_ctz(f2) * S] : kNoEntry;
+            const int bestLevel2 = a2 == kNoEntry ? -1 : ent_oct(a2);
+            const int bestDist2 = a2 == kNoEntry ? 256 : ent_dist(a2);
+            if (ent_oct(a1) == bestLevel2 && (float)ent_dist(a1) > P.nnratio * (float)bestDist2) a = false;
+        }
+        c1 = a1;
+        exh = x;
+        acc = a;
+    }
+    // what later threads and the commit see of the choice
+    __device__ __forceinline__ unsigned sig() const { return exh ? kTrunc : (acc ? c1 : kNoEntry); }
+};
+
+// One re-scoring pass over X, the ballot (not empty) of this wave's lanes whose lists ran
+// out, against the current claims sfmp: a lone lane by the whole wave, otherwise the
+// first four lanes of X by one 16-lane row each.  Any list that is exact against the
+// claims of some moment stays valid later (claims only ever block more keypoints), so
+// lanes beyond the one that stopped the commit may be re-scored in the same pass.  `mine`:
+// each lane's own query; first: the lowest lane of X.  The lanes served (returned: how many,
+// the lowest of X) start over on their new lists.  nrescore, the caller's count of re-scored
+// lists, is raised here, before the new lists are set up, and not from the returned count:
+// kept live across relist() the count costs the 1024-thread k_proj_search forms a spilled
+// register each.  Whole wave active.
+template <int S>
+__device__ __forceinline__ int replay_rescore(const ProjProblem& pb, const ProjParams& P, const SortedGrid& G,
+                                              const int* sfmp, const QueryReg& mine, unsigned long long X,
+                                              int first, ReplayList<S>& L, int& nrescore) {
+    const int lastp = pb.n > 0 ? pb.n - 1 : 0;
+    const int lane = threadIdx.x & 63;
+    unsigned ne[kTopK];
+    if (__popcll(X) > 1) {
+        // rows 0..3 take the first four exhausted lanes
+        const int row = lane >> 4;
+        unsigned long long x = X;
+        for (int r = 0; r < row; r++) x &= x - 1;
+        const bool valid = x != 0;
+        const int src = valid ? __ffsll((long long)x) - 1 : first;
+        score_groupk<16>(pb, P, shfl_query(mine, src), valid, G, sfmp, ne);
+        const int myrow = __popcll(X & ((1ull << lane) - 1));
+        const bool take = ((X >> lane) & 1ull) && myrow < 4;
+#pragma unroll
+        for (int j = 0; j < kTopK; j++) {
+            const unsigned v = (unsigned)__shfl((int)ne[j], (myrow & 3) * 16);
+            if (take) L.e[j] = v;
+        }
+        nrescore += __popcll(X) < 4 ? __popcll(X) : 4;
+        if (take) L.relist(P, lastp);
+        return __popcll(X) < 4 ? __popcll(X) : 4;
+    }
+    score_groupk<64>(pb, P, bcast_query(mine, first), true, G, sfmp, ne);  // wave-uniform result
+#pragma unroll
+    for (int j = 0; j < kTopK; j++)
+        if (lane == first) L.e[j] = ne[j];
+    nrescore++;
+    if (lane == first) L.relist(P, lastp);
+    return 1;
+}
+
+// A committed match is recorded with its query; the rotation bins are computed after the
+// replay, off the sequential path.  cm: the ballot of this wave's committing lanes; base:
+// the records before this wave's.
+__device__ __forceinline__ void replay_record(bool com, unsigned long long cm, int base, int pos, int q, int* mlist,
+                                              int* mbin) {
+    if (com) {
+        const int r = base + __popcll(cm & ((1ull << (threadIdx.x & 63)) - 1));
+        mlist[r] = pos;
+        mbin[r] = q;
+    }
+}
+
+// The orientation check over the nrec recorded matches (complete and visible to every
+// calling thread), thread t of `stride`: rotHist of the committed matches (ORBmatcher.cc:
+// 1750-1757, bin of query angle - keypoint angle; integer counts, so the order of the
+// additions is immaterial), ComputeThreeMaxima (every thread, same result) and the
+// un-matching of the other bins (ORBmatcher.cc:1770-1786).  sync(): makes the callers'
+// s_hist additions visible to each other.  Returns how many matches this thread removed.
+template <typename AngleFn, typename SyncFn>
+__device__ __forceinline__ int replay_rot_check(int t, int stride, int nrec, const int* mlist, int* mbin,
+                                                const float* qang, int* s_hist, int* sfmp, AngleFn angle_of,
+                                                SyncFn sync) {
+    for (int m = t; m < nrec; m += stride) {
+        const int bin = rot_bin(qang[mbin[m]], angle_of(mlist[m]));
+        mbin[m] = bin;
+        atomicAdd(&s_hist[bin], 1);
+    }
+    sync();
+    const RotMaxima rm = three_maxima(s_hist);
+    int bad = 0;
+    for (int m = t; m < nrec; m += stride) {
+        if (!rm.keeps(mbin[m])) {
+            sfmp[mlist[m]] = -1;
+            bad++;
+        }
+    }
+    return bad;
+}
+
+// Wave 0's replay of one problem over the per-query candidate lists qk (kTopK entries per
+// query) built by the scoring phase, 64 queries at a time.  sfmp / owner: the claims and
+// the owner map by sorted position (LDS, owner initialised to 0x7fffffff); elist: kTopK x
+// 64 words of LDS; angle_of(p): the angle of the keypoint at sorted position p.  Whole
+// wave active.  (The previous form committed the chunk's prefix before its first conflict
+// per round: configs[4] 447 rounds and 796 us per problem against 191 iterations and
+// 445 us for this one, configs[1] 73 -> 59 us.)
 template <typename AngleFn>
 __device__ void proj_replay(const ProjProblem& pb, const ProjParams& P, const SortedGrid& G, int* sfmp, int* owner,
                             unsigned* elist, const uint4* qk, const int* qmp, const float* qang, int* mlist,
@@ -1018,117 +1170,19 @@ __device__ void proj_replay(const ProjProblem& pb, const ProjParams& P, const So
     int nmatch = 0, nrec = 0, nrescore = 0, niter = 0, ntrunc = 0;
     // diagnostics (stamps): re-scoring, chunk loads + first round, chunk loads alone
     unsigned long long t_res = 0, t_first = 0, t_load = 0;
-    const float factor = kHistoLength / 360.0f;
-    const int need = P.ratio_mode ? 2 : 1;
-    const unsigned long long below = (1ull << lane) - 1;
-    // Fixpoint form.  The reference's loop is a function of the query order: query l's
-    // choice (first two unclaimed entries, acceptance) depends only on the claims of the
-    // queries before it.  Within a 64-query chunk every lane evaluates its choice against
-    // the committed claims plus the current proposals of the earlier lanes (an LDS owner
-    // map: owner[p] = lowest lane proposing p), and all lanes re-evaluate together until
-    // no lane changes (Jacobi iteration: after t iterations the first t lanes are final,
-    // so it converges, and its fixpoint is the sequential result).  A chunk with k
-    // independent conflicts then costs one iteration plus the longest dependency chain,
-    // not k rounds.  A lane whose list ran out stops the commit (it is re-scored against
-    // the committed claims); a lane accepting a MapPoint whose claim does not block (a11:
-    // Observations() == 0) does not -- later lanes ignore its proposal, and the commit
-    // keeps the last claim of a keypoint.
-    const int lastp = pb.n > 0 ? pb.n - 1 : 0;
     int guard = 0;
-    // a chunk's lists, MapPoints and queries (the latter for a re-scoring) are loaded
-    // while the chunk before it replays
-    uint4 nx_l[kListVec];
-    int nx_mp = -1;
-    QueryReg nx_q;
-    // Unconditional loads (a clamped index; nx_ok marks the real ones): a load under a
-    // per-lane branch makes the compiler merge its registers at the join, which waits for
-    // the data at once and turns the prefetch into a stall.
-    bool nx_ok = false;
-    auto fetch = [&](int qn) {
-        const int qc = min(qn, nq - 1);  // nq >= 1 wherever fetch runs
-        nx_ok = qn < nq;
-        nx_q = load_query(pb, qc);
-        nx_mp = qmp[qc];
-#pragma unroll
-        for (int v = 0; v < kListVec; v++) nx_l[v] = qk[kListVec * qc + v];
-    };
-    if (nq > 0) fetch(lane);
+    ReplayPrefetch nx;
+    const int lastp = pb.n > 0 ? pb.n - 1 : 0;
+    ReplayList<64> L(elist, lane);
+    if (nq > 0) nx.fetch(pb, qk, qmp, lane);
     for (int base = 0; base < nq && guard >= 0; base += 64) {
         const int q = base + lane;
         const unsigned long long t_chunk = st ? wall_clock64() : 0;
-        int mp = nx_ok ? nx_mp : -1;
-        unsigned e[kTopK];
-#pragma unroll
-        for (int v = 0; v < kListVec; v++) {
-            e[4 * v] = mp >= 0 ? nx_l[v].x : kNoEntry;
-            e[4 * v + 1] = mp >= 0 ? nx_l[v].y : kNoEntry;
-            e[4 * v + 2] = mp >= 0 ? nx_l[v].z : kNoEntry;
-            e[4 * v + 3] = mp >= 0 ? nx_l[v].w : kNoEntry;
-        }
-        const QueryReg mine = nx_q;  // consumed only by a re-scoring
-        fetch(q + 64);
-        // Per lane, derived once per list (at the chunk's start and after a re-scoring):
-        // the list itself in LDS (elist[j][lane]: an entry is picked by a per-lane index,
-        // conflict-free), its entries' owner-map slots, vm = the real entries (bits), full =
-        // it may hide unlisted candidates, lastgt = its last real entry is beyond the
-        // acceptance threshold.
-        unsigned vm = 0;
-        bool full = false, lastgt = false;
-        int oa[kTopK];
-        auto set_list = [&]() {
-            vm = 0;
-            int lastd = -1;
-#pragma unroll
-            for (int j = 0; j < kTopK; j++) {
-                elist[j * 64 + lane] = e[j];
-                oa[j] = min(ent_pos(e[j]), lastp);
-                vm |= (e[j] < kTrunc ? 1u : 0u) << j;
-                if (e[j] < kTrunc) lastd = ent_dist(e[j]);
-            }
-            full = e[kTopK - 1] != kNoEntry;
-            lastgt = lastd > P.accept_th;
-        };
-        set_list();
-        // this lane's claims block later queries (a11: only a MapPoint with observations)
-        bool bself = false;
-        // cblk bit j: entry j is taken by a committed claim (the claims before the chunk:
-        // one batch of independent LDS reads, and Observations() loads for a11)
-        unsigned cblk = 0;
-        if (mp >= 0) {
-            bself = claim_blocks(mp);
-#pragma unroll
-            for (int j = 0; j < kTopK; j++) cblk |= (claim_blocks(sfmp[oa[j]]) ? 1u : 0u) << j;
-        }
-        // a lane's choice given the blocked entries bm: c1 (its best free entry), whether
-        // it accepts c1, and whether its list ran out (exhausted: unlisted candidates may
-        // be the answer).  Bit arithmetic on the free mask; c1 / c2 read from elist.
-        unsigned c1 = kNoEntry;
-        bool exh = false, acc = false;
-        auto eval = [&](unsigned bm) {
-            const unsigned fm = vm & ~bm;
-            const int cnt = __popc(fm);
-            const unsigned a1 = fm ? elist[__builtin_ctz(fm) * 64 + lane] : kNoEntry;
-            // a full (or truncated) list may hide unlisted candidates -- but they are at
-            // least as far as its last exact entry (the list holds the smallest keys), so
-            // when that entry, or the free c1 of a ratio test, is already beyond the
-            // acceptance threshold the query stays unmatched
-            bool x = full && cnt < need;
-            if (x && ((cnt == 0 && lastgt) || (cnt == 1 && ent_dist(a1) > P.accept_th))) x = false;
-            bool a = !x && fm != 0 && ent_dist(a1) <= P.accept_th;
-            if (a && P.ratio_mode) {
-                const unsigned f2 = fm & (fm - 1);
-                const unsigned a2 = f2 ? elist[__builtin_ctz(f2) * 64 + lane] : kNoEntry;
-                const int bestLevel2 = a2 == kNoEntry ? -1 : ent_oct(a2);
-                const int bestDist2 = a2 == kNoEntry ? 256 : ent_dist(a2);
-                if (ent_oct(a1) == bestLevel2 && (float)ent_dist(a1) > P.nnratio * (float)bestDist2) a = false;
-            }
-            c1 = a1;
-            exh = x;
-            acc = a;
-        };
-        // what later lanes and the commit see of a lane's choice
-        auto sig = [&]() { return exh ? kTrunc : (acc ? c1 : kNoEntry); };
-        if (mp >= 0) eval(cblk);
+        L.load(nx);
+        const QueryReg mine = nx.q;  // consumed only by a re-scoring
+        nx.fetch(pb, qk, qmp, q + 64);
+        L.start(P, lastp, sfmp);
+        const int mp = L.mp;
         if (st) t_load += wall_clock64() - t_chunk;
         int start = 0;
         int ow[kTopK];
@@ -1140,48 +1194,42 @@ __device__ void proj_replay(const ProjProblem& pb, const ProjParams& P, const So
                 break;
             }
             const bool act = lane >= start && mp >= 0;
-            const int prop = act && acc && bself ? ent_pos(c1) : -1;
-            const unsigned old = sig();
+            const int prop = act && L.acc && L.bself ? ent_pos(L.c1) : -1;
+            const unsigned old = L.sig();
             // owner[p] = lowest lane proposing p (LDS ops of a wave are executed in order:
             // all atomics, then all reads, then the reset)
             if (prop >= 0) atomicMin(&owner[prop], lane);
 #pragma unroll
-            for (int j = 0; j < kTopK; j++) ow[j] = owner[oa[j]];  // every lane: no exec-masked reads
+            for (int j = 0; j < kTopK; j++) ow[j] = owner[L.oa[j]];  // every lane: no exec-masked reads
             if (prop >= 0) owner[prop] = 0x7fffffff;
             // bit j: entry j proposed by an earlier lane (ow - lane < 0; ow >= 0, lane < 64)
             unsigned sb = 0;
 #pragma unroll
             for (int j = 0; j < kTopK; j++) sb |= ((unsigned)(ow[j] - lane) >> 31) << j;
-            if (act) eval(cblk | sb);
-            if (__ballot(act && sig() != old)) continue;
+            if (act) L.eval(P, L.cblk | sb);
+            if (__ballot(act && L.sig() != old)) continue;
             // fixpoint: every active lane's choice is the sequential one up to the first
             // exhausted lane f
-            const unsigned long long sm = __ballot(act && exh);
+            const unsigned long long sm = __ballot(act && L.exh);
             const int f = sm ? __ffsll((long long)sm) - 1 : 64;
-            const bool com = act && acc && lane < f;
+            const bool com = act && L.acc && lane < f;
             const unsigned long long comm = __ballot(com);
             // Blocking claims are unique (a later lane saw them).  A non-blocking claim
             // (a11: Observations() == 0) may be taken again by a later lane of the same
             // commit, which then keeps the keypoint (ORBmatcher.cc:117-119, 167): it is
             // written only by the last lane claiming its keypoint (owner map: the lowest
             // 63 - lane, in order: atomics, reads, reset).
-            if (com && bself) sfmp[ent_pos(c1)] = mp;
-            if (__ballot(com && !bself)) {
-                const int pp = com ? ent_pos(c1) : 0;
+            if (com && L.bself) sfmp[ent_pos(L.c1)] = mp;
+            if (__ballot(com && !L.bself)) {
+                const int pp = com ? ent_pos(L.c1) : 0;
                 if (com) atomicMin(&owner[pp], 63 - lane);
                 const int lo = owner[pp];
                 if (com) owner[pp] = 0x7fffffff;
-                if (com && !bself && lo == 63 - lane) sfmp[pp] = mp;
+                if (com && !L.bself && lo == 63 - lane) sfmp[pp] = mp;
             }
             nmatch += __popcll(comm);
             if (P.check_ori) {
-                // the match is recorded with its query; the rotation bins are computed
-                // after the replay, off the sequential path
-                if (com) {
-                    const int r = nrec + __popcll(comm & below);
-                    mlist[r] = ent_pos(c1);
-                    mbin[r] = q;
-                }
+                replay_record(com, comm, nrec, ent_pos(L.c1), q, mlist, mbin);
                 nrec += __popcll(comm);
             }
             if (st && first) t_first += wall_clock64() - t_chunk;
@@ -1190,56 +1238,21 @@ __device__ void proj_replay(const ProjProblem& pb, const ProjParams& P, const So
             // the committed lanes' claims, for the lanes after them: the entries a lane
             // below f proposed (blocking proposals only reach the owner map)
 #pragma unroll
-            for (int j = 0; j < kTopK; j++) cblk |= (act && lane >= f ? (unsigned)(ow[j] - f) >> 31 : 0u) << j;
+            for (int j = 0; j < kTopK; j++) L.cblk |= (act && lane >= f ? (unsigned)(ow[j] - f) >> 31 : 0u) << j;
             start = f;
             {
-                // lane f's list ran out: re-score it against the current claims.  Any list
-                // that is exact against the claims of some moment stays valid later
-                // (claims only ever block more keypoints), so the other exhausted lanes
-                // of the chunk are re-scored in the same pass, one 16-lane row each.
+                // lane f's list ran out: re-score it against the current claims, and the
+                // chunk's other exhausted lanes in the same pass
                 const unsigned long long t0 = st ? wall_clock64() : 0;
                 wave_lds_fence();
-                unsigned long long X = __ballot(act && exh && lane >= f);
+                const unsigned long long X = __ballot(act && L.exh && lane >= f);
                 if (st) {  // diagnostics: the list ran out at a truncation, not at its last entry
                     bool tr = false;
 #pragma unroll
-                    for (int j = 0; j < kTopK; j++) tr = tr || e[j] == kTrunc;
+                    for (int j = 0; j < kTopK; j++) tr = tr || L.e[j] == kTrunc;
                     ntrunc += __builtin_amdgcn_readlane((int)tr, f);
                 }
-                unsigned ne[kTopK];
-                if (__popcll(X) > 1) {
-                    // rows 0..3 take the first four exhausted lanes
-                    const int row = lane >> 4;
-                    unsigned long long x = X;
-                    for (int r = 0; r < row; r++) x &= x - 1;
-                    const bool valid = x != 0;
-                    const int src = valid ? __ffsll((long long)x) - 1 : f;
-                    score_groupk<16>(pb, P, shfl_query(mine, src), valid, G, sfmp, ne);
-                    const int myrow = __popcll(X & below);
-                    const bool mine_row = ((X >> lane) & 1ull) && myrow < 4;
-#pragma unroll
-                    for (int j = 0; j < kTopK; j++) {
-                        const unsigned v = (unsigned)__shfl((int)ne[j], (myrow & 3) * 16);
-                        if (mine_row) e[j] = v;
-                    }
-                    nrescore += __popcll(X) < 4 ? __popcll(X) : 4;
-                    if (mine_row) {
-                        cblk = 0;
-                        set_list();
-                        eval(0);
-                    }
-                } else {
-                    score_groupk<64>(pb, P, bcast_query(mine, f), true, G, sfmp, ne);  // wave-uniform result
-#pragma unroll
-                    for (int j = 0; j < kTopK; j++)
-                        if (lane == f) e[j] = ne[j];
-                    nrescore++;
-                    if (lane == f) {
-                        cblk = 0;  // the new list holds free keypoints only
-                        set_list();
-                        eval(0);   // lane f is the first active lane: no earlier proposals
-                    }
-                }
+                replay_rescore(pb, P, G, sfmp, mine, X, f, L, nrescore);
                 if (st) t_res += wall_clock64() - t0;
             }
             wave_lds_fence();
@@ -1252,46 +1265,10 @@ __device__ void proj_replay(const ProjProblem& pb, const ProjParams& P, const So
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();
     if (P.check_ori) {
-        // rotHist of the committed matches (ORBmatcher.cc:1750-1757): bin of (query angle
-        // - keypoint angle); integer counts, so the order of the additions is immaterial
-        for (int m = lane; m < nrec; m += 64) {
-            const int tpos = mlist[m];
-            float rot = qang[mbin[m]] - angle_of(tpos);
-            if (rot < 0.0f) rot += 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == kHistoLength) bin = 0;
-            mbin[m] = bin;
-            atomicAdd(&s_hist[bin], 1);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (P.check_ori) {
-        // ComputeThreeMaxima, ORBmatcher.cc:1935-1977
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < kHistoLength; i++) {
-            const int s = s_hist[i];
-            if (s > max1) {
-                max3 = max2; max2 = max1; max1 = s;
-                ind3 = ind2; ind2 = ind1; ind1 = i;
-            } else if (s > max2) {
-                max3 = max2; max2 = s;
-                ind3 = ind2; ind2 = i;
-            } else if (s > max3) {
-                max3 = s;
-                ind3 = i;
-            }
-        }
-        if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-        int bad = 0;
-        for (int m = lane; m < nrec; m += 64) {
-            const int b = mbin[m];
-            if (b != ind1 && b != ind2 && b != ind3) {
-                sfmp[mlist[m]] = -1;
-                bad++;
-            }
-        }
+        int bad = replay_rot_check(lane, 64, nrec, mlist, mbin, qang, s_hist, sfmp, angle_of, [] {
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+        });
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
         nmatch -= bad;
@@ -1310,8 +1287,8 @@ __device__ void proj_replay(const ProjProblem& pb, const ProjParams& P, const So
     }
 }
 
-// The replay over RT threads (RT / 64 waves): the fixpoint of proj_replay over chunks of
-// RT queries instead of 64.  The iterations a chunk takes are set by its longest
+// The replay over RT threads (RT / 64 waves): the fixpoint over chunks of RT queries
+// instead of 64.  The iterations a chunk takes are set by its longest
 // dependency chain, not by its size, so wider chunks mean fewer iterations per query;
 // every exhausted list of a chunk is re-scored at the first sequence point (each wave
 // its own lanes, four per 16-lane-row pass), so a chunk rarely stops twice.
@@ -1330,10 +1307,6 @@ __device__ void proj_replay_block(const ProjProblem& pb, const ProjParams& P, co
     __shared__ int s_bad;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nq = pb.nq;
-    const int lastp = pb.n > 0 ? pb.n - 1 : 0;
-    const int need = P.ratio_mode ? 2 : 1;
-    const unsigned long long below = (1ull << lane) - 1;
-    const float factor = kHistoLength / 360.0f;
     int nmatch = 0, nrec = 0, nrescore = 0, niter = 0, nstop = 0;  // block-uniform
     // diagnostics (stamps, thread 0's clock): chunk loads, fixpoint rounds, commits, re-scoring
     unsigned long long t_load = 0, t_round = 0, t_commit = 0, t_res = 0, tc = 0;
@@ -1342,23 +1315,10 @@ __device__ void proj_replay_block(const ProjProblem& pb, const ProjParams& P, co
     long long guard = 0;
     bool broken = false;
     if (tid == 0) s_key = 0x7fffffff;
-    // a chunk's lists, MapPoints and queries are loaded while the chunk before it replays
-    uint4 nx_l[kListVec];
-    int nx_mp = -1;
-    QueryReg nx_q;
-    // Unconditional loads (a clamped index; nx_ok marks the real ones): a load under a
-    // per-lane branch makes the compiler merge its registers at the join, which waits for
-    // the data at once and turns the prefetch into a stall.
-    bool nx_ok = false;
-    auto fetch = [&](int qn) {
-        const int qc = min(qn, nq - 1);  // nq >= 1 wherever fetch runs
-        nx_ok = qn < nq;
-        nx_q = load_query(pb, qc);
-        nx_mp = qmp[qc];
-#pragma unroll
-        for (int v = 0; v < kListVec; v++) nx_l[v] = qk[kListVec * qc + v];
-    };
-    if (nq > 0) fetch(tid);
+    ReplayPrefetch nx;
+    const int lastp = pb.n > 0 ? pb.n - 1 : 0;
+    ReplayList<RT> L(elist, tid);
+    if (nq > 0) nx.fetch(pb, qk, qmp, tid);
     __syncthreads();
     for (int base = 0; base < nq && !broken; base += RT) {
         if (it > (1u << 20)) {  // keep iteration << 10 in 31 bits: restart the tags
@@ -1368,63 +1328,11 @@ __device__ void proj_replay_block(const ProjProblem& pb, const ProjParams& P, co
         }
         const int q = base + tid;
         if (clk) tc = wall_clock64();
-        const int mp = nx_ok ? nx_mp : -1;
-        unsigned e[kTopK];
-#pragma unroll
-        for (int v = 0; v < kListVec; v++) {
-            e[4 * v] = mp >= 0 ? nx_l[v].x : kNoEntry;
-            e[4 * v + 1] = mp >= 0 ? nx_l[v].y : kNoEntry;
-            e[4 * v + 2] = mp >= 0 ? nx_l[v].z : kNoEntry;
-            e[4 * v + 3] = mp >= 0 ? nx_l[v].w : kNoEntry;
-        }
-        const QueryReg mine = nx_q;
-        fetch(q + RT);
-        unsigned vm = 0;
-        bool full = false, lastgt = false;
-        int oa[kTopK];
-        auto set_list = [&]() {
-            vm = 0;
-            int lastd = -1;
-#pragma unroll
-            for (int j = 0; j < kTopK; j++) {
-                elist[j * RT + tid] = e[j];
-                oa[j] = min(ent_pos(e[j]), lastp);
-                vm |= (e[j] < kTrunc ? 1u : 0u) << j;
-                if (e[j] < kTrunc) lastd = ent_dist(e[j]);
-            }
-            full = e[kTopK - 1] != kNoEntry;
-            lastgt = lastd > P.accept_th;
-        };
-        set_list();
-        bool bself = false;
-        unsigned cblk = 0;
-        if (mp >= 0) {
-            bself = claim_blocks(mp);
-#pragma unroll
-            for (int j = 0; j < kTopK; j++) cblk |= (claim_blocks(sfmp[oa[j]]) ? 1u : 0u) << j;
-        }
-        unsigned c1 = kNoEntry;
-        bool exh = false, acc = false;
-        auto eval = [&](unsigned bm) {
-            const unsigned fm = vm & ~bm;
-            const int cnt = __popc(fm);
-            const unsigned a1 = fm ? elist[__builtin_ctz(fm) * RT + tid] : kNoEntry;
-            bool x = full && cnt < need;
-            if (x && ((cnt == 0 && lastgt) || (cnt == 1 && ent_dist(a1) > P.accept_th))) x = false;
-            bool a = !x && fm != 0 && ent_dist(a1) <= P.accept_th;
-            if (a && P.ratio_mode) {
-                const unsigned f2 = fm & (fm - 1);
-                const unsigned a2 = f2 ? elist[__builtin_ctz(f2) * RT + tid] : kNoEntry;
-                const int bestLevel2 = a2 == kNoEntry ? -1 : ent_oct(a2);
-                const int bestDist2 = a2 == kNoEntry ? 256 : ent_dist(a2);
-                if (ent_oct(a1) == bestLevel2 && (float)ent_dist(a1) > P.nnratio * (float)bestDist2) a = false;
-            }
-            c1 = a1;
-            exh = x;
-            acc = a;
-        };
-        auto sig = [&]() { return exh ? kTrunc : (acc ? c1 : kNoEntry); };
-        if (mp >= 0) eval(cblk);
+        L.load(nx);
+        const QueryReg mine = nx.q;
+        nx.fetch(pb, qk, qmp, q + RT);
+        L.start(P, lastp, sfmp);
+        const int mp = L.mp;
         if (clk) {
             const unsigned long long t = wall_clock64();
             t_load += t - tc;
@@ -1440,36 +1348,36 @@ __device__ void proj_replay_block(const ProjProblem& pb, const ProjParams& P, co
             }
             it++;
             const bool act = tid >= start && mp >= 0;
-            const unsigned old = sig();
-            if (act && acc && bself) atomicMax(&owner[ent_pos(c1)], (it << 10) | (unsigned)(1023 - tid));
+            const unsigned old = L.sig();
+            if (act && L.acc && L.bself) atomicMax(&owner[ent_pos(L.c1)], (it << 10) | (unsigned)(1023 - tid));
             __syncthreads();
 #pragma unroll
-            for (int j = 0; j < kTopK; j++) ow[j] = owner[oa[j]];
+            for (int j = 0; j < kTopK; j++) ow[j] = owner[L.oa[j]];
             // bit j: entry j proposed this iteration by a thread before this one
             unsigned sb = 0;
 #pragma unroll
             for (int j = 0; j < kTopK; j++)
                 sb |= ((ow[j] >> 10) == it && (int)(1023u - (ow[j] & 1023u)) < tid ? 1u : 0u) << j;
-            if (act) eval(cblk | sb);
-            if (__syncthreads_or(act && sig() != old)) continue;
+            if (act) L.eval(P, L.cblk | sb);
+            if (__syncthreads_or(act && L.sig() != old)) continue;
             if (clk) {
                 const unsigned long long t = wall_clock64();
                 t_round += t - tc;
                 tc = t;
             }
             // fixpoint: the first exhausted thread f stops the commit (a non-blocking
-            // acceptor does not: see proj_replay)
-            int key = act && exh ? tid : 0x7fffffff;
+            // acceptor does not: ReplayList)
+            int key = act && L.exh ? tid : 0x7fffffff;
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) key = min(key, __shfl_xor(key, o));
             if (lane == 0 && key != 0x7fffffff) atomicMin(&s_key, key);
             __syncthreads();
             const int K = s_key;
             const int f = K == 0x7fffffff ? RT : K;
-            const bool com = act && acc && tid < f;
-            if (com && bself) sfmp[ent_pos(c1)] = mp;  // unique
+            const bool com = act && L.acc && tid < f;
+            if (com && L.bself) sfmp[ent_pos(L.c1)] = mp;  // unique
             const unsigned long long cm = __ballot(com);
-            const bool wnb = __ballot(com && !bself) != 0;
+            const bool wnb = __ballot(com && !L.bself) != 0;
             if (lane == 0) s_wc[wave] = __popcll(cm) | (wnb ? 1 << 16 : 0);
             __syncthreads();
             if (tid == 0) s_key = 0x7fffffff;  // read by every thread before the barrier above
@@ -1487,16 +1395,12 @@ __device__ void proj_replay_block(const ProjProblem& pb, const ProjParams& P, co
                 // writes it (a fresh tag iteration, highest thread wins)
                 it++;
                 const unsigned tag = (it << 10) | (unsigned)tid;
-                if (com) atomicMax(&owner[ent_pos(c1)], tag);
+                if (com) atomicMax(&owner[ent_pos(L.c1)], tag);
                 __syncthreads();
-                if (com && !bself && owner[ent_pos(c1)] == tag) sfmp[ent_pos(c1)] = mp;
+                if (com && !L.bself && owner[ent_pos(L.c1)] == tag) sfmp[ent_pos(L.c1)] = mp;
                 __syncthreads();  // publishes sfmp for the re-scoring and the next chunk
             }
-            if (P.check_ori && com) {
-                const int r = nrec + woff + __popcll(cm & below);
-                mlist[r] = ent_pos(c1);
-                mbin[r] = q;
-            }
+            if (P.check_ori) replay_record(com, cm, nrec + woff, ent_pos(L.c1), q, mlist, mbin);
             nmatch += tot;
             if (P.check_ori) nrec += tot;
             if (clk) {
@@ -1510,50 +1414,16 @@ __device__ void proj_replay_block(const ProjProblem& pb, const ProjParams& P, co
             if (act && tid >= f) {
 #pragma unroll
                 for (int j = 0; j < kTopK; j++)
-                    cblk |= ((ow[j] >> 10) == itf && (int)(1023u - (ow[j] & 1023u)) < f ? 1u : 0u) << j;
+                    L.cblk |= ((ow[j] >> 10) == itf && (int)(1023u - (ow[j] & 1023u)) < f ? 1u : 0u) << j;
             }
             start = f;
             {
                 // every exhausted list at or after f, against the current claims (sfmp is
                 // published by the barrier above)
-                unsigned long long X = __ballot(act && exh && tid >= f);
+                unsigned long long X = __ballot(act && L.exh && tid >= f);
                 while (X) {
-                    unsigned ne[kTopK];
-                    if (__popcll(X) == 1) {
-                        const int src = __ffsll((long long)X) - 1;
-                        score_groupk<64>(pb, P, bcast_query(mine, src), true, G, sfmp, ne);
-#pragma unroll
-                        for (int j = 0; j < kTopK; j++)
-                            if (lane == src) e[j] = ne[j];
-                        nrescore++;
-                        if (lane == src) {
-                            cblk = 0;
-                            set_list();
-                            eval(0);
-                        }
-                        X = 0;
-                    } else {
-                        const int row = lane >> 4;
-                        unsigned long long x = X;
-                        for (int r = 0; r < row; r++) x &= x - 1;
-                        const bool valid = x != 0;
-                        const int src = valid ? __ffsll((long long)x) - 1 : 0;
-                        score_groupk<16>(pb, P, shfl_query(mine, src), valid, G, sfmp, ne);
-                        const int myrow = __popcll(X & below);
-                        const bool take = ((X >> lane) & 1ull) && myrow < 4;
-#pragma unroll
-                        for (int j = 0; j < kTopK; j++) {
-                            const unsigned v = (unsigned)__shfl((int)ne[j], (myrow & 3) * 16);
-                            if (take) e[j] = v;
-                        }
-                        nrescore += __popcll(X) < 4 ? __popcll(X) : 4;
-                        if (take) {
-                            cblk = 0;
-                            set_list();
-                            eval(0);
-                        }
-                        for (int r = 0; r < 4 && X; r++) X &= X - 1;
-                    }
+                    const int served = replay_rescore(pb, P, G, sfmp, mine, X, __ffsll((long long)X) - 1, L, nrescore);
+                    for (int r = 0; r < served; r++) X &= X - 1;
                 }
             }
             if (st) __syncthreads();  // diagnostics: every wave's re-scoring done before the clock
@@ -1568,43 +1438,10 @@ __device__ void proj_replay_block(const ProjProblem& pb, const ProjParams& P, co
     // every thread keeps the same counters; the match list is complete after the barrier
     __syncthreads();
     if (P.check_ori && !broken) {
-        // rotHist of the committed matches (ORBmatcher.cc:1750-1757)
-        for (int m = tid; m < nrec; m += RT) {
-            const int tpos = mlist[m];
-            float rot = qang[mbin[m]] - angle_of(tpos);
-            if (rot < 0.0f) rot += 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == kHistoLength) bin = 0;
-            mbin[m] = bin;
-            atomicAdd(&s_hist[bin], 1);
-        }
-        if (tid == 0) s_bad = 0;
-        __syncthreads();
-        // ComputeThreeMaxima, ORBmatcher.cc:1935-1977 (every thread, same result)
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < kHistoLength; i++) {
-            const int s = s_hist[i];
-            if (s > max1) {
-                max3 = max2; max2 = max1; max1 = s;
-                ind3 = ind2; ind2 = ind1; ind1 = i;
-            } else if (s > max2) {
-                max3 = max2; max2 = s;
-                ind3 = ind2; ind2 = i;
-            } else if (s > max3) {
-                max3 = s;
-                ind3 = i;
-            }
-        }
-        if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-        int bad = 0;
-        for (int m = tid; m < nrec; m += RT) {
-            const int b = mbin[m];
-            if (b != ind1 && b != ind2 && b != ind3) {
-                sfmp[mlist[m]] = -1;
-                bad++;
-            }
-        }
+        int bad = replay_rot_check(tid, RT, nrec, mlist, mbin, qang, s_hist, sfmp, angle_of, [&] {
+            if (tid == 0) s_bad = 0;
+            __syncthreads();
+        });
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
         if (lane == 0 && bad) atomicAdd(&s_bad, bad);
@@ -1666,29 +1503,12 @@ __device__ __forceinline__ SortedGrid seq_grid(unsigned char* base, const SeqGri
 // QLDS: per-query state in LDS; otherwise in the problem's global scratch.
 // SPLIT: no replay here -- the sorted grid is published to `grids` (SeqGridLayout, no
 // sorted descriptors) and k_seq_commit replays with one wave and a small LDS footprint.
-// Register budgets (waves per SIMD) of the batched sequence matcher's two kernels, which run
-// beside the extraction lanes: every VGPR they hold for their whole launch is one the
-// extraction's waves on that SIMD cannot have.  0: the compiler's choice (100 VGPRs for
-// the scoring kernel).  The scoring kernel at 5 (96 VGPRs, 20 B of spill) measured +1-2 %
-// at configs[4] before the octree split (r05p) and within noise after it (r05af); 6 and 8
-// (more spills) and the commit at 3 or 4 measured slower (r05p).
-#ifndef ORBX_SCORE_WPE
-#define ORBX_SCORE_WPE 0
-#endif
-#ifndef ORBX_COMMIT_WPE
-#define ORBX_COMMIT_WPE 0
-#endif
-#if ORBX_SCORE_WPE
-#define ORBX_SCORE_ATTR __attribute__((amdgpu_waves_per_eu(ORBX_SCORE_WPE)))
-#else
-#define ORBX_SCORE_ATTR
-#endif
-#if ORBX_COMMIT_WPE
-#define ORBX_COMMIT_ATTR __attribute__((amdgpu_waves_per_eu(ORBX_COMMIT_WPE)))
-#else
-#define ORBX_COMMIT_ATTR
-#endif
-
+// Register budgets (waves per SIMD, amdgpu_waves_per_eu) of the batched sequence matcher's
+// two kernels, which run beside the extraction lanes: every VGPR they hold for their whole
+// launch is one the extraction's waves on that SIMD cannot have.  Both keep the compiler's
+// choice (100 VGPRs for the scoring kernel).  The scoring kernel at 5 (96 VGPRs, 20 B of
+// spill) measured +1-2 % at configs[4] before the octree split (r05p) and within noise after
+// it (r05af); 6 and 8 (more spills) and the commit at 3 or 4 measured slower (r05p).
 template <bool QLDS, bool DLDS, int NT, bool SPLIT>
 __device__ __forceinline__ void proj_search_body(const ProjProblem* __restrict__ probs, ProjParams P,
                                                  unsigned long long* __restrict__ scratch,
@@ -1704,19 +1524,12 @@ __device__ __forceinline__ void proj_search_body(const ProjProblem* __restrict__
     const int n = pb.n, nq = pb.nq;
     unsigned long long* st = P.stamps ? P.stamps + kStampWords * blockIdx.x : nullptr;
     if (st && tid == 0) st[0] = wall_clock64();
-    constexpr bool kXyGlobal = SPLIT && kSplitSxyGlobal;
-    const ProjLds L(n, nq, DLDS, QLDS, P.noct, !SPLIT, !kXyGlobal);
+    const ProjLds L(n, nq, DLDS, QLDS, P.noct, !SPLIT);
     unsigned* skey = (unsigned*)(smem + L.skey);
     uint16_t* colstart = (uint16_t*)(smem + L.colstart);
     uint16_t* bstart = (uint16_t*)(smem + L.bstart);
     uint16_t* orun = (uint16_t*)(smem + L.orun);
-    float2* sxy;
-    if constexpr (kXyGlobal) {
-        const SeqGridLayout gl(gcap, P.noct);
-        sxy = (float2*)(grids + (size_t)blockIdx.x * gl.total + gl.sxy);
-    } else {
-        sxy = (float2*)(smem + L.sxy);
-    }
+    float2* sxy = (float2*)(smem + L.sxy);
     int* sfmp = (int*)(smem + L.sfmp);
     int* owner = (int*)(smem + L.owner);
     float* sang = (float*)(smem + L.sang);
@@ -1776,14 +1589,14 @@ __device__ __forceinline__ void proj_search_body(const ProjProblem* __restrict__
     // count of their window widths -- KR 4 for at most ~4 columns, 8 for ~8, 16 beyond --
     // which are the exact classes when the queries come in octave order (TrackWithMotion-
     // Model's LastFrame keypoints are level-major) and otherwise only a cost heuristic: the
-    // lists do not depend on KR.  ORBX_SCORE_KR_FIXED=1 builds the round-4 choice.
+    // lists do not depend on KR.
     __shared__ int s_qcut[2];
     // Pyramids of up to 8 levels keep KR 8 for every query: the classes measured slower
     // there (configs[1] 227.8-228.4k -> 224.3-225.9k frames/s) and faster above
     // (configs[4] 108.2-108.3k -> 111.1-111.3k; r05c, interleaved on one box).
     // The split scoring (the sequence matcher beside the extraction) gives every query the
     // same kSplitKr lanes instead.
-    const bool one_kr = ORBX_SCORE_KR_FIXED || P.noct <= 8 || (SPLIT && kSplitKr > 0);  // uniform over the workgroup
+    const bool one_kr = P.noct <= 8 || (SPLIT && kSplitKr > 0);  // uniform over the workgroup
     __shared__ int s_next;  // score_pairs' query counter
     if (tid < 2) s_qcut[tid] = one_kr && tid == 1 && P.noct <= 8 ? nq : 0;
     if (tid == 0) s_next = 0;
@@ -1807,7 +1620,8 @@ __device__ __forceinline__ void proj_search_body(const ProjProblem* __restrict__
     }
     __syncthreads();
     const int qcut4 = s_qcut[0], qcut8 = s_qcut[1];
-    constexpr bool kPrefetch = !SPLIT || ORBX_SPLIT_PREFETCH;  // the next queries' loads during the current ones
+    // the next queries' loads during the current ones (not in the split scoring: kSplitLaneTopK's note)
+    constexpr bool kPrefetch = !SPLIT;
     auto pass = [&](auto kr, int q0, int q1) {
         constexpr int KR = decltype(kr)::value;
         constexpr int kQw = 64 / KR;  // queries per wave and pass
@@ -1838,7 +1652,7 @@ __device__ __forceinline__ void proj_search_body(const ProjProblem* __restrict__
     if constexpr (SPLIT && kSplitKr > 0) {
         // pyramids above eight levels: the pairs without lockstep (configs[4] RGB-D +2.2 %; at
         // configs[1] they measured 1 % slower than the lockstep pairs, r06pq)
-        if (ORBX_SPLIT_PERSIST && P.noct > 8)
+        if (P.noct > 8)
             score_pairs(pb, P, G, qk, qmp, qang, &s_next);
         else
             pass(std::integral_constant<int, (kSplitKr > 0 ? kSplitKr : 1)>{}, 0, nq);
@@ -1856,7 +1670,7 @@ __device__ __forceinline__ void proj_search_body(const ProjProblem* __restrict__
         for (int p = tid; p < n; p += NT) {
             ((unsigned*)(gb + gl.skey))[p] = skey[p] & ~kKeyBlocked;
             ((uint16_t*)(gb + gl.orun))[p] = orun[p];
-            if (!kXyGlobal) ((float2*)(gb + gl.sxy))[p] = sxy[p];
+            ((float2*)(gb + gl.sxy))[p] = sxy[p];
             ((float*)(gb + gl.sang))[p] = ldg(&pb.keys[sk_idx(skey[p])].angle);
         }
         for (int t = tid; t < nb; t += NT) ((uint16_t*)(gb + gl.bstart))[t] = bstart[t];
@@ -1878,14 +1692,6 @@ __global__ __launch_bounds__(NT) void k_proj_search(const ProjProblem* __restric
                                                     const long long* __restrict__ scratch_off,
                                                     unsigned char* __restrict__ grids, int gcap) {
     proj_search_body<QLDS, DLDS, NT, SPLIT>(probs, P, scratch, scratch_off, grids, gcap);
-}
-
-// the sequence matcher's scoring form (beside the extraction lanes) with its register budget
-template <>
-__global__ __launch_bounds__(kSplitScoreThreads) ORBX_SCORE_ATTR void k_proj_search<false, false, kSplitScoreThreads, true>(
-    const ProjProblem* __restrict__ probs, ProjParams P, unsigned long long* __restrict__ scratch,
-    const long long* __restrict__ scratch_off, unsigned char* __restrict__ grids, int gcap) {
-    proj_search_body<false, false, kSplitScoreThreads, true>(probs, P, scratch, scratch_off, grids, gcap);
 }
 
 // ---- the batched sequence matcher in three launches (orbx_match_sequence_device)
@@ -2009,17 +1815,15 @@ __global__ __launch_bounds__(kSeqScoreThreads) void k_seq_score(const ProjProble
 }
 
 template <int RT>
-__global__ __launch_bounds__(RT) ORBX_COMMIT_ATTR void k_seq_commit(const ProjProblem* __restrict__ probs, ProjParams P,
+__global__ __launch_bounds__(RT) void k_seq_commit(const ProjProblem* __restrict__ probs, ProjParams P,
                                                    unsigned char* __restrict__ grids, int cap,
                                                    unsigned long long* __restrict__ scratch,
                                                    const long long* __restrict__ scratch_off, int use_sdesc) {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ int s_hist[kHistoLength];
-#ifndef ORBX_NO_REPLAY_PRIO
     // the replay is latency-bound and shares its CU with the extraction's throughput
     // waves: the highest wave priority makes the SIMD's arbiter issue its instructions first
     __builtin_amdgcn_s_setprio(3);
-#endif
     const ProjProblem pb = probs[blockIdx.x];
     if (pb.nq < 0) return;  // skipped by the retry pass (k_seq_score's workgroups leave on nq too)
     unsigned long long* st = P.stamps ? P.stamps + kStampWords * blockIdx.x : nullptr;  // diagnostics
@@ -2441,8 +2245,7 @@ hipError_t launch_proj_search(const ProjProblem* d_probs, int nprob, const ProjP
         if (small) return hipErrorInvalidValue;
         dlds = qlds = false;
     }
-    const size_t lds = ProjLds(max_n, max_nq, dlds, qlds, P.noct, split_grids == nullptr,
-                               !(split_grids && kSplitSxyGlobal)).total;
+    const size_t lds = ProjLds(max_n, max_nq, dlds, qlds, P.noct, split_grids == nullptr).total;
     if (lds > limit) return hipErrorInvalidValue;
     const void* fn;
     const int nt = tiny ? kProjThreadsTiny : (small ? kProjThreadsSmall : (split_grids ? kSplitScoreThreads : kProjThreads));
@@ -2572,7 +2375,6 @@ __global__ __launch_bounds__(kTriThreads) void k_triangulation(const TriProblem*
         // sequential walk reads them back by v_readlane, so only a claimed best (a
         // re-score against the current vbMatched2) touches global memory.
         int nrec = 0;
-        const float factor = kHistoLength / 360.0f;
         for (int q0 = 0; q0 < pb.nq; q0 += 64) {
             const int ql = q0 + lane;
             int l_idx1 = 0, l_idx2 = -1;
@@ -2610,10 +2412,7 @@ __global__ __launch_bounds__(kTriThreads) void k_triangulation(const TriProblem*
                 if (pb.check_ori) {
                     const unsigned long long comm = __ballot(com);
                     if (com) {
-                        float rot = l_a1 - l_a2;
-                        if (rot < 0.0f) rot += 360.0f;
-                        int bin = (int)roundf(rot * factor);
-                        if (bin == kHistoLength) bin = 0;
+                        const int bin = rot_bin(l_a1, l_a2);
                         const int r = nrec + __popcll(comm & ((1ull << lane) - 1ull));
                         mlist[r] = l_idx1;
                         mbin[r] = bin;
@@ -2638,11 +2437,8 @@ __global__ __launch_bounds__(kTriThreads) void k_triangulation(const TriProblem*
                         matched2[idx2] = 1;
                     }
                     if (pb.check_ori) {
-                        float rot = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(l_a1), f)) -
-                                    pb.keys2[idx2].angle;
-                        if (rot < 0.0f) rot += 360.0f;
-                        int bin = (int)roundf(rot * factor);
-                        if (bin == kHistoLength) bin = 0;
+                        const int bin = rot_bin(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(l_a1), f)),
+                                                pb.keys2[idx2].angle);
                         if (lane == 0) {
                             mlist[nrec] = idx1;
                             mbin[nrec] = bin;
@@ -2658,26 +2454,9 @@ __global__ __launch_bounds__(kTriThreads) void k_triangulation(const TriProblem*
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         if (pb.check_ori) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < kHistoLength; i++) {
-                const int s = s_hist[i];
-                if (s > max1) {
-                    max3 = max2; max2 = max1; max1 = s;
-                    ind3 = ind2; ind2 = ind1; ind1 = i;
-                } else if (s > max2) {
-                    max3 = max2; max2 = s;
-                    ind3 = ind2; ind2 = i;
-                } else if (s > max3) {
-                    max3 = s;
-                    ind3 = i;
-                }
-            }
-            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-            for (int m = lane; m < nrec; m += 64) {
-                const int b = mbin[m];
-                if (b != ind1 && b != ind2 && b != ind3) pb.matches12[mlist[m]] = -1;
-            }
+            const RotMaxima rm = three_maxima(s_hist);
+            for (int m = lane; m < nrec; m += 64)
+                if (!rm.keeps(mbin[m])) pb.matches12[mlist[m]] = -1;
         }
         if (pb.pairs_out) {
             // vMatchedPairs (cc:1045-1053): vMatches12 compacted in idx1 order, 64 at a time
