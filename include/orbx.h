@@ -825,6 +825,63 @@ int orbx_kfdb_detect_loop_candidates(orbx_kfdb* db, const int32_t* word, const d
                                      const int32_t* connected, int nconnected, float min_score, int32_t* cand,
                                      int max_cand, int* ncand);
 
+/* ---- Optimizer::PoseOptimization: motion-only bundle adjustment after the searches ----
+ * Optimizer::PoseOptimization(Frame*) (src/Optimizer.cc:299-502) with the parts of g2o it
+ * runs (OptimizationAlgorithmLevenberg, the dense 6x6 LDLT, EdgeSE3ProjectXYZOnlyPose /
+ * EdgeStereoSE3ProjectXYZOnlyPose, RobustKernelHuber, SE3Quat), for B Frames in HBM in one
+ * launch: one persistent workgroup per frame runs the four rounds of up to ten
+ * Levenberg-Marquardt iterations.  Float inputs are widened to double, everything after
+ * is double.  Sums over edges have a fixed shape (no floating-point atomics): a frame's
+ * results are the same bytes whatever the batch around it.  DESIGN.md §4.15.
+ *   Edges, in keypoint order: keypoint i with a MapPoint (frame_mp[i] in [0, n_mp); -1 or
+ *   an id outside the table is NULL) is monocular if u_right is NULL or u_right[i] < 0
+ *   (cc:346), stereo otherwise; information = I * inv_level_sigma2[octave] (an octave
+ *   outside [0, nlevels) is clamped into it).
+ *   Outputs: Tcw_opt (Converter::toCvMat of the recovered SE3Quat); outlier = mvbOutlier
+ *   (in/out: entries of keypoints without a MapPoint are left as they are); ninliers = the
+ *   return value nInitialCorrespondences - nBad; ninit = nInitialCorrespondences; trace
+ *   (nullable) per round {LM iterations run, linear solves tried}, 0 for rounds not run.
+ *   Fewer than 3 edges (cc:428): ninliers 0, Tcw_opt = Tcw, the flags of the keypoints
+ *   with MapPoints cleared.
+ *   Epilogue (Tracking.cc:1004-1017), optional: discard_outliers sets the outliers'
+ *   frame_mp entries to -1 and clears their flags; nmatches_map (nullable) counts the
+ *   inliers whose MapPoint has Observations() > 0 (mp_obs [n_mp], NULL: every one has).
+ * inv_level_sigma2 is a host array; every other pointer is a device pointer.  Asynchronous
+ * on `stream` (or the matcher's). */
+#define ORBX_POSE_OPT_LDS_EDGES 1984 /* frames of up to this many edges keep them in LDS */
+typedef struct {
+    int batch;
+    const orbx_keypoint* kps;       /* [B][cap] mvKeysUn */
+    const int32_t* n;               /* [B] keypoint counts */
+    int cap;
+    const float* u_right;           /* [B][cap] mvuRight or NULL (every edge monocular) */
+    int32_t* frame_mp;              /* [B][cap] mvpMapPoints as MapPoint ids; written only with discard_outliers */
+    int n_mp;                       /* MapPoints in the table */
+    const float* mp_pos;            /* [n_mp][3] GetWorldPos() */
+    const float* inv_level_sigma2;  /* host: mvInvLevelSigma2 (nlevels) */
+    int nlevels;
+    float fx, fy, cx, cy, bf;
+    const float* Tcw;               /* [B][12] mTcw rows 0..2 */
+    float* Tcw_opt;                 /* [B][12] out */
+    uint8_t* outlier;               /* [B][cap] in/out */
+    int32_t* ninliers;              /* [B] out */
+    int32_t* ninit;                 /* [B] out */
+    int32_t* trace;                 /* [B][4][2] out or NULL */
+    int discard_outliers;
+    const int32_t* mp_obs;          /* [n_mp] Observations() or NULL */
+    int32_t* nmatches_map;          /* [B] out or NULL */
+} orbx_pose_optimization_batch;
+int orbx_pose_optimization_batch_device(orbx_matcher* m, const orbx_pose_optimization_batch* po, void* stream);
+
+/* The drop-in single-frame call on host arrays (keys [n], u_right [n] or NULL, frame_mp
+ * [n], mp_pos [n_mp][3], Tcw [12] in; Tcw_opt [12], outlier [n] (in/out), *ninit, trace
+ * [4][2] (nullable), *ninliers out): one upload, the batch kernel with B = 1, one
+ * synchronisation.  The same bytes as the batch form gives for that frame. */
+int orbx_pose_optimization(orbx_matcher* m, const orbx_keypoint* keys, int n, const float* u_right,
+                           const int32_t* frame_mp, const float* mp_pos, int n_mp, const float* inv_level_sigma2,
+                           int nlevels, float fx, float fy, float cx, float cy, float bf, const float* Tcw,
+                           float* Tcw_opt, uint8_t* outlier, int* ninit, int32_t* trace, int* ninliers);
+
 /* Alternative kernel forms and diagnostics switches, process-wide (tests and A/B tools;
  * the product reads no environment).  Names: "pz_seg" (pyramid levels per launch, 0 = one
  * launch), "pz_byte" (byte-read k_pyramid), "desc_tiles" (tile-major describe),

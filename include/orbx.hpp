@@ -237,6 +237,33 @@ inline void ComputeStereoFromRGBD(const orbx_camera& cam, const std::vector<orbx
                                         mDepthMapFactor, mbf, mvKeysUn.data(), mvuRight.data(), mvDepth.data()));
 }
 
+// Optimizer (include/Optimizer.h): the one g2o call on the per-frame path.
+// PoseOptimization(Frame*) (src/Optimizer.cc:299-502) on the Frame's arrays: mvKeysUn,
+// mvuRight (empty: monocular), mvpMapPoints as MapPoint ids (-1 = NULL) into the positions
+// mpPos (GetWorldPos(), 3 floats per id), mvInvLevelSigma2, fx fy cx cy mbf and mTcw (rows
+// 0..2, 12 floats, updated in place as SetPose does).  mvbOutlier is resized to the keypoints
+// and updated; returns nInitialCorrespondences - nBad.  trace (optional, 8 ints): per round
+// the LM iterations run and the linear solves tried.  Runs on the matcher's handle and stream.
+class Optimizer {
+public:
+    static int PoseOptimization(ORBmatcher& matcher, const std::vector<orbx_keypoint>& mvKeysUn,
+                                const std::vector<float>& mvuRight, const std::vector<int32_t>& mvpMapPoints,
+                                const std::vector<float>& mpPos, const std::vector<float>& mvInvLevelSigma2, float fx,
+                                float fy, float cx, float cy, float mbf, float* mTcw, std::vector<uint8_t>& mvbOutlier,
+                                int32_t* trace = nullptr, int* nInitialCorrespondences = nullptr) {
+        const int n = (int)mvKeysUn.size();
+        mvbOutlier.resize((size_t)n, 0);
+        float out[12];
+        int inliers = 0;
+        check(orbx_pose_optimization(matcher.handle(), mvKeysUn.data(), n, mvuRight.empty() ? nullptr : mvuRight.data(),
+                                     mvpMapPoints.data(), mpPos.data(), (int)(mpPos.size() / 3),
+                                     mvInvLevelSigma2.data(), (int)mvInvLevelSigma2.size(), fx, fy, cx, cy, mbf, mTcw,
+                                     out, mvbOutlier.data(), nInitialCorrespondences, trace, &inliers));
+        for (int i = 0; i < 12; i++) mTcw[i] = out[i];
+        return inliers;
+    }
+};
+
 // DBoW2::BowVector (BowVector.h:59-62): word id -> value, ascending.
 typedef std::map<int32_t, double> BowVector;
 

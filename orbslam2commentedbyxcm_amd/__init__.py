@@ -9,5 +9,6 @@ reference's ORBextractor / ORBmatcher interface.
 from ._lib import KEYPOINT_DTYPE, OrbxError, lib  # noqa: F401
 from .database import KeyFrameDatabase  # noqa: F401
 from .extractor import ORBextractor  # noqa: F401
+from .optimizer import PoseOptimizer  # noqa: F401
 
-__all__ = ["ORBextractor", "KeyFrameDatabase", "KEYPOINT_DTYPE", "OrbxError", "lib"]
+__all__ = ["ORBextractor", "KeyFrameDatabase", "PoseOptimizer", "KEYPOINT_DTYPE", "OrbxError", "lib"]

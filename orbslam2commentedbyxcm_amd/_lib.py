@@ -55,7 +55,7 @@ EXPORTED = [
     "orbx_kfdb_add_batch_device", "orbx_kfdb_add", "orbx_kfdb_erase", "orbx_kfdb_clear", "orbx_kfdb_set_covisibility",
     "orbx_kfdb_reloc_scores", "orbx_kfdb_score_device", "orbx_kfdb_detect_relocalization_candidates_device",
     "orbx_kfdb_detect_loop_candidates_device", "orbx_kfdb_detect_relocalization_candidates",
-    "orbx_kfdb_detect_loop_candidates",
+    "orbx_kfdb_detect_loop_candidates", "orbx_pose_optimization_batch_device", "orbx_pose_optimization",
 ]
 
 ORBX_DEPTH_U16 = 0
@@ -108,6 +108,20 @@ class LocalMapBatch(C.Structure):
                 ("scale_factors", C.POINTER(C.c_float)), ("local_off", C.POINTER(C.c_int32)),
                 ("local_ids", C.c_void_p), ("th", C.c_float), ("viewing_cos_limit", C.c_float),
                 ("frame_mp", C.c_void_p), ("nmatches", C.c_void_p)]
+
+
+class PoseOptimizationBatch(C.Structure):
+    """orbx_pose_optimization_batch."""
+    _fields_ = [("batch", C.c_int), ("kps", C.c_void_p), ("n", C.c_void_p), ("cap", C.c_int),
+                ("u_right", C.c_void_p), ("frame_mp", C.c_void_p), ("n_mp", C.c_int), ("mp_pos", C.c_void_p),
+                ("inv_level_sigma2", C.POINTER(C.c_float)), ("nlevels", C.c_int), ("fx", C.c_float),
+                ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float), ("Tcw", C.c_void_p),
+                ("Tcw_opt", C.c_void_p), ("outlier", C.c_void_p), ("ninliers", C.c_void_p), ("ninit", C.c_void_p),
+                ("trace", C.c_void_p), ("discard_outliers", C.c_int), ("mp_obs", C.c_void_p),
+                ("nmatches_map", C.c_void_p)]
+
+
+ORBX_POSE_OPT_LDS_EDGES = 1984
 
 
 # ---- handle lifetime (DESIGN.md §1 "Teardown") ------------------------------------
@@ -299,6 +313,9 @@ def lib() -> C.CDLL:
                                                           vp, vp, vp, vp]
     L.orbx_kfdb_detect_relocalization_candidates.argtypes = [vp, i32p, dp, C.c_int, i32p, C.c_int, ip]
     L.orbx_kfdb_detect_loop_candidates.argtypes = [vp, i32p, dp, C.c_int, i32p, C.c_int, C.c_float, i32p, C.c_int, ip]
+    L.orbx_pose_optimization_batch_device.argtypes = [vp, C.POINTER(PoseOptimizationBatch), vp]
+    L.orbx_pose_optimization.argtypes = [vp, vp, C.c_int, fp, i32p, fp, C.c_int, fp, C.c_int, C.c_float, C.c_float,
+                                         C.c_float, C.c_float, C.c_float, fp, fp, u8p, ip, i32p, ip]
     L.orbx_version.restype = C.c_char_p
     L.orbx_device_count.argtypes = [ip]
     L.orbx_last_error.restype = C.c_char_p

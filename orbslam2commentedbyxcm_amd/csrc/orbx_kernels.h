@@ -114,6 +114,37 @@ hipError_t launch_window_best(const BestProblem* d_prob, int nq, hipStream_t str
 hipError_t launch_distinctive(int nmp, const int32_t* off, const uint8_t* desc, int32_t* best, uint8_t* out_desc,
                               hipStream_t stream);
 
+// k_pose_opt (orbx_poseopt.hip): Optimizer::PoseOptimization for `batch` frames, one workgroup
+// each.  Frames of up to kPoseOptLdsEdges edges keep their edge records in LDS (64 KB: two
+// workgroups per compute unit), larger ones stream them from the workspace.
+constexpr int kPoseOptLdsEdges = ORBX_POSE_OPT_LDS_EDGES;
+struct PoseOptArgs {
+    const orbx_keypoint* kps;  // [B][cap]
+    const int32_t* n;          // [B]
+    int cap;
+    const float* u_right;      // [B][cap] or null
+    int32_t* frame_mp;         // [B][cap]
+    const float* pos;          // [n_mp][3]
+    int n_mp;
+    float inv_sigma2[ORBX_MAX_LEVELS];
+    int nlevels;
+    float fx, fy, cx, cy, bf;
+    float delta_mono, delta_stereo;
+    const float* Tcw;          // [B][12]
+    float* Tcw_out;            // [B][12]
+    uint8_t* outlier;          // [B][cap]
+    int32_t* ninliers;         // [B]
+    int32_t* ninit;            // [B]
+    int32_t* trace;            // [B][4][2] or null
+    int discard_outliers;
+    const int32_t* mp_obs;     // [n_mp] or null
+    int32_t* nmatches_map;     // [B] or null
+    float* rec;                // set by launch_pose_opt
+    int32_t* eidx;
+};
+size_t pose_opt_workspace_bytes(int batch, int cap);
+hipError_t launch_pose_opt(PoseOptArgs A, int batch, char* workspace, hipStream_t stream);
+
 hipError_t launch_window_match(const uint8_t* qdesc, int nq, const uint8_t* tdesc, const int32_t* tlevel,
                                const int32_t* cand_off, const int32_t* cand, int tie_last,
                                int32_t* best_idx, int32_t* best_dist, int32_t* best_level,

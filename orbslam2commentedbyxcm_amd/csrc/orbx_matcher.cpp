@@ -228,6 +228,11 @@ struct orbx_matcher {
     // queries, problems and grids of orbx_search_local_points_device (device-only)
     char* lscr = nullptr;
     size_t lscr_cap = 0;
+    // edge records of orbx_pose_optimization_batch_device, and the single call's frame (device-only)
+    char* pscr = nullptr;
+    size_t pscr_cap = 0;
+    char* pstage = nullptr;
+    size_t pstage_cap = 0;
     StageRing stage;
     // wall time of the newest drop-in host call (entry to return), as a C++ caller sees it
     double last_call_us = 0.0;
@@ -435,6 +440,8 @@ void orbx_matcher_destroy(orbx_matcher* m) {
     if (m->dscr) (void)hipFree(m->dscr);
     if (m->tscr) (void)hipFree(m->tscr);
     if (m->lscr) (void)hipFree(m->lscr);
+    if (m->pscr) (void)hipFree(m->pscr);
+    if (m->pstage) (void)hipFree(m->pstage);
     m->stage.release();
     if (m->hmp) (void)hipHostFree(m->hmp);
     for (auto& slot : m->ev)
@@ -2029,6 +2036,134 @@ int orbx_compute_stereo_matches_batch_device(orbx_matcher* m, orbx_extractor* ex
         HIP_TRY(hipEventRecord(ev[1], s));
         m->ncalls++;
     }
+    return ORBX_OK;
+}
+
+// Optimizer::PoseOptimization for a batch of Frames in HBM (see include/orbx.h)
+int orbx_pose_optimization_batch_device(orbx_matcher* m, const orbx_pose_optimization_batch* po, void* stream) {
+    if (!m || !po) return fail(ORBX_ERR_ARG, "null argument");
+    const int B = po->batch, cap = po->cap;
+    if (B < 0 || cap <= 0 || po->n_mp < 0 || po->nlevels < 1 || po->nlevels > ORBX_MAX_LEVELS ||
+        !po->inv_level_sigma2)
+        return fail(ORBX_ERR_ARG, "bad argument");
+    if (B == 0) return ORBX_OK;
+    if (!po->kps || !po->n || !po->frame_mp || !po->Tcw || !po->Tcw_opt || !po->outlier || !po->ninliers ||
+        !po->ninit || (po->n_mp > 0 && !po->mp_pos))
+        return fail(ORBX_ERR_ARG, "null buffer");
+    if ((size_t)B * (size_t)cap >= ((size_t)1 << 31)) return fail(ORBX_ERR_ARG, "batch x cap of 2^31 or more");
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+    const size_t need = pose_opt_workspace_bytes(B, cap);
+    if (m->pscr_cap < need) {
+        HIP_TRY(hipStreamSynchronize(s));
+        if (m->pscr) HIP_TRY(hipFree(m->pscr));
+        m->pscr = nullptr;
+        m->pscr_cap = 0;
+        HIP_TRY(hipMalloc((void**)&m->pscr, need));
+        m->pscr_cap = need;
+    }
+    PoseOptArgs A{};
+    A.kps = po->kps;
+    A.n = po->n;
+    A.cap = cap;
+    A.u_right = po->u_right;
+    A.frame_mp = po->frame_mp;
+    A.pos = po->mp_pos;
+    A.n_mp = po->n_mp;
+    for (int l = 0; l < po->nlevels; l++) A.inv_sigma2[l] = po->inv_level_sigma2[l];
+    A.nlevels = po->nlevels;
+    A.fx = po->fx;
+    A.fy = po->fy;
+    A.cx = po->cx;
+    A.cy = po->cy;
+    A.bf = po->bf;
+    A.delta_mono = (float)std::sqrt(5.991);    // Optimizer.cc:332
+    A.delta_stereo = (float)std::sqrt(7.815);  // Optimizer.cc:334
+    A.Tcw = po->Tcw;
+    A.Tcw_out = po->Tcw_opt;
+    A.outlier = po->outlier;
+    A.ninliers = po->ninliers;
+    A.ninit = po->ninit;
+    A.trace = po->trace;
+    A.discard_outliers = po->discard_outliers;
+    A.mp_obs = po->mp_obs;
+    A.nmatches_map = po->nmatches_map;
+    HIP_TRY(launch_pose_opt(A, B, m->pscr, s));
+    return ORBX_OK;
+}
+
+// The single-frame host form: one staged frame, the batch kernel, one synchronisation.
+int orbx_pose_optimization(orbx_matcher* m, const orbx_keypoint* keys, int n, const float* u_right,
+                           const int32_t* frame_mp, const float* mp_pos, int n_mp, const float* inv_level_sigma2,
+                           int nlevels, float fx, float fy, float cx, float cy, float bf, const float* Tcw,
+                           float* Tcw_opt, uint8_t* outlier, int* ninit, int32_t* trace, int* ninliers) {
+    if (!m || n < 0 || n_mp < 0 || nlevels < 1 || nlevels > ORBX_MAX_LEVELS || !inv_level_sigma2 || !Tcw || !Tcw_opt ||
+        !ninliers || (n > 0 && (!keys || !frame_mp || !outlier)) || (n_mp > 0 && !mp_pos))
+        return fail(ORBX_ERR_ARG, "bad argument");
+    CallClock clock(m);
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    const int cap = n > 0 ? n : 1;
+    const size_t nt = (size_t)(n_mp > 0 ? n_mp : 1);
+    // inputs, then the outputs as one block: Tcw_opt [12], ninliers, ninit, trace [8], outlier [cap]
+    const size_t o_keys = 0, o_ur = o_keys + pad(sizeof(orbx_keypoint) * cap), o_mp = o_ur + pad(4 * (size_t)cap),
+                 o_pos = o_mp + pad(4 * (size_t)cap), o_in = o_pos + pad(12 * nt), o_out = o_in + pad(64),
+                 out_bytes = 12 * 4 + 2 * 4 + 8 * 4 + (size_t)cap, total = o_out + pad(out_bytes);
+    if (m->pstage_cap < total) {
+        HIP_TRY(hipStreamSynchronize(s));
+        if (m->pstage) HIP_TRY(hipFree(m->pstage));
+        m->pstage = nullptr;
+        m->pstage_cap = 0;
+        HIP_TRY(hipMalloc((void**)&m->pstage, total));
+        m->pstage_cap = total;
+    }
+    char* p = m->pstage;
+    // pageable sources: staged by the runtime before each call returns
+    if (n > 0) {
+        HIP_TRY(hipMemcpyAsync(p + o_keys, keys, sizeof(orbx_keypoint) * n, hipMemcpyHostToDevice, s));
+        if (u_right) HIP_TRY(hipMemcpyAsync(p + o_ur, u_right, 4 * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p + o_mp, frame_mp, 4 * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p + o_out + 88, outlier, (size_t)n, hipMemcpyHostToDevice, s));
+    }
+    if (n_mp > 0) HIP_TRY(hipMemcpyAsync(p + o_pos, mp_pos, 12 * (size_t)n_mp, hipMemcpyHostToDevice, s));
+    int32_t in[16] = {};
+    std::memcpy(in, Tcw, 48);
+    in[12] = n;
+    HIP_TRY(hipMemcpyAsync(p + o_in, in, sizeof(in), hipMemcpyHostToDevice, s));
+    orbx_pose_optimization_batch po{};
+    po.batch = 1;
+    po.kps = (const orbx_keypoint*)(p + o_keys);
+    po.n = (const int32_t*)(p + o_in) + 12;
+    po.cap = cap;
+    po.u_right = u_right ? (const float*)(p + o_ur) : nullptr;
+    po.frame_mp = (int32_t*)(p + o_mp);
+    po.n_mp = n_mp;
+    po.mp_pos = (const float*)(p + o_pos);
+    po.inv_level_sigma2 = inv_level_sigma2;
+    po.nlevels = nlevels;
+    po.fx = fx;
+    po.fy = fy;
+    po.cx = cx;
+    po.cy = cy;
+    po.bf = bf;
+    po.Tcw = (const float*)(p + o_in);
+    po.Tcw_opt = (float*)(p + o_out);
+    po.ninliers = (int32_t*)(p + o_out + 48);
+    po.ninit = (int32_t*)(p + o_out + 52);
+    po.trace = (int32_t*)(p + o_out + 56);
+    po.outlier = (uint8_t*)(p + o_out + 88);
+    const int rc = orbx_pose_optimization_batch_device(m, &po, s);
+    if (rc) return rc;
+    std::vector<char> h(out_bytes);
+    HIP_TRY(hipMemcpyAsync(h.data(), p + o_out, out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::memcpy(Tcw_opt, h.data(), 48);
+    int32_t counts[2];
+    std::memcpy(counts, h.data() + 48, 8);
+    *ninliers = counts[0];
+    if (ninit) *ninit = counts[1];
+    if (trace) std::memcpy(trace, h.data() + 56, 32);
+    if (n > 0) std::memcpy(outlier, h.data() + 88, (size_t)n);
     return ORBX_OK;
 }
 

@@ -40,7 +40,7 @@ class SequencePipeline:
                  lane_offset_stage: int | None = None, match_cu_stride: int = 1,
                  match_priority: int = 0, on_matched=None, local_map: bool = False, local_window: int = 3,
                  local_th: float = 1.0, level0_in_place: bool = True, retry_below: int = 20,
-                 first_in_phase: bool = True):
+                 first_in_phase: bool = True, pose_opt: bool = False):
         import torch
 
         self.B, self.W, self.H = int(batch), int(width), int(height)
@@ -115,6 +115,17 @@ class SequencePipeline:
             self.tab = [mappoint_table(B, cap, self.dev) for _ in range(nbuf)]
             self.nm_local = [torch.empty((B,), **i32) for _ in range(nbuf)]
             self._lt = []  # (start, end) event pairs of the local stage while timing
+        # pose_opt: Optimizer::PoseOptimization (Tracking.cc:1000) of every frame after the search
+        # and its retry, on the matcher's stream; results() gains Tcw_opt, outlier, ninliers,
+        # nmatches_map.  The monocular search then runs on a MapPoint table (ids (b-1)*cap + i,
+        # as with local_map) instead of the depth-on-ray form, so that the edges have positions.
+        self.pose_opt = None
+        if pose_opt and self.match:
+            from .optimizer import PoseOptStage
+            self.pose_opt = PoseOptStage(self.matcher, nbuf, B, cap, self.dev, self.exs[0].GetInverseScaleSigmaSquares())
+            if not self.local_map and self._pose_opt_table():
+                from .matcher import mappoint_table
+                self.tab = [mappoint_table(B, cap, self.dev) for _ in range(nbuf)]
         self.ev_ex = [[torch.cuda.Event() for _ in range(self.S)] for _ in range(nbuf)]  # [buffer][lane]
         self.ev_m = [torch.cuda.Event() for _ in range(nbuf)]
         self.used = [False] * nbuf
@@ -192,6 +203,10 @@ class SequencePipeline:
             self.ev_ex[b][c].record(self.streams[c])
         self.used[b] = True
 
+    def _pose_opt_table(self) -> bool:
+        """Whether the monocular search needs a MapPoint table of its own for pose_opt."""
+        return True
+
     def _lane_tail(self, b, c):
         """Per-frame work a subclass enqueues on lane c's stream after its extraction of
         buffer b (before the event the matcher waits for)."""
@@ -206,11 +221,23 @@ class SequencePipeline:
                 stream_wait_event(self.ms.cuda_stream, ev)
         if self.local_map:
             self._match_local(b, Tcw)
+        elif self.pose_opt is not None:
+            from .matcher import create_mappoints_device
+            s = self.ms.cuda_stream
+            create_mappoints_device(self.kps[b], self.n[b], Tcw, self.sf, self.fx, self.fy, self.cx, self.cy,
+                                    self.tab[b], const_depth=self.depth, stream=s)
+            self.matcher.match_sequence_device_ex(self.kps[b], self.desc[b], self.n[b], Tcw, self.mp[b], self.nm[b],
+                                                  self.sf, self.fx, self.fy, self.cx, self.cy, self.W, self.H,
+                                                  th=self.th, d_mp_pos=self.tab[b]["pos"], global_ids=True,
+                                                  retry_below=self.retry_below, stream=s)
         else:
             self.matcher.match_sequence_device_ex(self.kps[b], self.desc[b], self.n[b], Tcw, self.mp[b], self.nm[b],
                                                   self.sf, self.fx, self.fy, self.cx, self.cy, self.W, self.H,
                                                   depth=self.depth, th=self.th, retry_below=self.retry_below,
                                                   stream=self.ms.cuda_stream)
+        if self.pose_opt is not None:
+            self.pose_opt.run(b, self.kps[b], self.n[b], self.mp[b], self.tab[b]["pos"], Tcw, self.fx, self.fy,
+                              self.cx, self.cy, stream=self.ms)
         if self.on_matched is not None:
             self.on_matched(b)
         self.ev_m[b].record(self.ms)
@@ -285,6 +312,8 @@ class SequencePipeline:
         r = {"kps": self.kps[b], "desc": self.desc[b], "n": self.n[b], "mp": self.mp[b], "nm": self.nm[b]}
         if self.local_map:
             r["nm_local"] = self.nm_local[b]
+        if self.pose_opt is not None:
+            r.update(self.pose_opt.results(b))
         return r
 
     def host_results(self, b=None) -> dict:
@@ -296,6 +325,9 @@ class SequencePipeline:
                "nm": r["nm"].cpu().numpy()}
         if "nm_local" in r:
             out["nm_local"] = r["nm_local"].cpu().numpy()
+        if self.pose_opt is not None:
+            for name in self.pose_opt.results(self.last if b is None else b):
+                out[name] = r[name].cpu().numpy()
         return out
 
     def status(self) -> np.ndarray:

@@ -22,8 +22,9 @@ Steps 2-3 run per frame on each extraction lane's stream right after its frames,
 on the matcher stream beside the next batch's extraction.  No frame of the
 sequence is a keyframe (UpdateLastFrame returns early for the last keyframe, Tracking.cc:
 902; a caller with keyframes passes their LastFrames' MapPoints through set_tracked and
-skips those frames' temporal points itself).  Optimizer::PoseOptimization, which consumes
-the matches in the reference, is out of scope: every frame's pose is given.
+skips those frames' temporal points itself).  Every frame's pose is given; with pose_opt=True
+Optimizer::PoseOptimization (Tracking.cc:1000) then runs on the matches from that pose
+(results: Tcw_opt, outlier, ninliers, nmatches_map); the optimised pose is not fed back.
 
 bench.py --workload tum5k times this object; tests/test_gpu_rgbd.py checks every frame
 and pair of its output against the CPU parity oracle.
@@ -109,6 +110,9 @@ class RGBDSequencePipeline(SequencePipeline):
                                  d_obs_in=None if self.obs_in is None else self.obs_in[b0:b1],
                                  d_pos_in=None if self.pos_in is None else self.pos_in[b0:b1], stream=stream)
 
+    def _pose_opt_table(self) -> bool:
+        return False  # the LastFrame table (UpdateLastFrame) holds the positions
+
     def _lane_tail(self, b, c):
         if self.frame_on_lanes:
             b0, b1 = self.bounds[c]
@@ -135,6 +139,9 @@ class RGBDSequencePipeline(SequencePipeline):
             self.cy, self.W, self.H, th=self.th, mono=False, bf=self.bf, b=self.mb, d_u_right=self.ur[b],
             d_mp_pos=lf["mp_pos"], d_has_mp=lf["has_mp"], d_mp_obs=lf["mp_obs"], global_ids=True,
             retry_below=self.retry_below, bounds=self.image_bounds, stream=s)
+        if self.pose_opt is not None:  # Tracking.cc:1000-1017 on mvKeysUn / mvuRight and the LastFrames' MapPoints
+            self.pose_opt.run(b, self.kpu[b], self.n[b], self.mp[b], lf["mp_pos"], T, self.fx, self.fy, self.cx,
+                              self.cy, bf=self.bf, d_u_right=self.ur[b], d_mp_obs=lf["mp_obs"], stream=self.ms)
         if self._timing:
             ev[1].record(self.ms)
             self._rt.append(ev)

@@ -46,7 +46,8 @@ class StereoSequencePipeline:
                  params=(2000, 1.2, 8, 20, 7), track: bool = True, th: float = 7.0, nnratio: float = 0.9,
                  check_ori: bool = True, th_depth_factor: float = 35.0, max_d: float | None = None,
                  matcher_mode: int | None = None, device: int = 0, level0_in_place: bool = True,
-                 retry_below: int = 20, nsets: int = 4, lane_offset_stage: int = 2, track_stream: bool = True):
+                 retry_below: int = 20, nsets: int = 4, lane_offset_stage: int = 2, track_stream: bool = True,
+                 pose_opt: bool = False):
         import torch
 
         from .extractor import stream_create
@@ -108,6 +109,15 @@ class StereoSequencePipeline:
                      "ur": torch.empty((B, cap), **f32), "dp": torch.empty((B, cap), **f32),
                      "mp": torch.empty((B, cap), **i32), "nm": torch.empty((B,), **i32),
                      **last_frame_table(B, cap, self.dev)} for _ in range(self.nsets)]
+        # pose_opt: Optimizer::PoseOptimization (Tracking.cc:1000) after the search and its retry,
+        # on the tracking stream; the sets' buffers gain Tcw_opt, outlier, ninliers, nmatches_map
+        self.pose_opt = None
+        if pose_opt and self.track:
+            from .optimizer import PoseOptStage
+            self.pose_opt = PoseOptStage(self.tmatcher, self.nsets, B, cap, self.dev,
+                                         self.sets[0][0].GetInverseScaleSigmaSquares())
+            for k in range(self.nsets):
+                self.buf[k].update(self.pose_opt.results(k))
         self.streams = [(torch.cuda.ExternalStream(a.stream_handle(), device=self.dev),
                          torch.cuda.ExternalStream(c.stream_handle(), device=self.dev)) for a, c in self.sets]
         self.ev_l = [torch.cuda.Event() for _ in range(self.nsets)]
@@ -182,6 +192,9 @@ class StereoSequencePipeline:
                 self.W, self.H, th=self.th, mono=False, bf=self.bf, b=self.b, d_u_right=bk["ur"],
                 d_mp_pos=bk["mp_pos"], d_has_mp=bk["has_mp"], d_mp_obs=bk["mp_obs"], global_ids=True,
                 retry_below=self.retry_below, stream=s)
+            if self.pose_opt is not None:
+                self.pose_opt.run(k, bk["kl"], bk["nl"], bk["mp"], bk["mp_pos"], d_Tcw, self.fx, self.fy, self.cx,
+                                  self.cy, bf=self.bf, d_u_right=bk["ur"], d_mp_obs=bk["mp_obs"], stream=self.ts)
         if self._timing:
             ev[2].record(self.ts)
             self._st.append(ev)
@@ -248,6 +261,13 @@ class StereoSequencePipeline:
         B, cap = self.B, self.cap
         kp = lambda t: t.cpu().numpy().view(np.uint8).reshape(B, cap, 28).view(L.KEYPOINT_DTYPE).reshape(B, cap)  # noqa
         out = {"kl": kp(bk["kl"]), "kr": kp(bk["kr"])}
-        for name in ("dl", "dr", "nl", "nr", "ur", "dp", "mp", "nm", "mp_obs", "mp_pos", "has_mp"):
+        names = ("dl", "dr", "nl", "nr", "ur", "dp", "mp", "nm", "mp_obs", "mp_pos", "has_mp")
+        if self.pose_opt is not None:
+            names += tuple(self.pose_opt.results(k))
+        for name in names:
             out[name] = bk[name].cpu().numpy()
         return out
+
+    def results(self, k=None) -> dict:
+        """Device tensors of set k (default: the newest step's); call after synchronising."""
+        return dict(self.buf[self.last if k is None else k])
