@@ -882,6 +882,118 @@ int orbx_pose_optimization(orbx_matcher* m, const orbx_keypoint* keys, int n, co
                            int nlevels, float fx, float fy, float cx, float cy, float bf, const float* Tcw,
                            float* Tcw_opt, uint8_t* outlier, int* ninit, int32_t* trace, int* ninliers);
 
+/* ---- Sim3Solver: Horn's closed form under RANSAC for a batch of loop candidates ----
+ * Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc:37-534) as LoopClosing::ComputeSim3
+ * drives it (LoopClosing.cc:243-377: one solver per candidate, iterate(5) round-robin), for B
+ * candidates in HBM: the link between orbx_search_by_bow_keyframes and orbx_search_by_sim3.
+ * Float inputs are widened to double, everything after is double, outputs are rounded to
+ * float once.  No sum crosses lanes in floating point: a candidate's results are the same
+ * bytes whatever the batch around it and however its iterations are cut into calls.  The
+ * host reads nothing back between a set and the end of an iterate.  DESIGN.md §4.16.
+ *
+ * The library owns no random generator: the caller supplies the three draws of every
+ * iteration (orbx_sim3_draws gives the reference's).
+ *
+ * orbx_sim3_create (the workspace and per-candidate state for up to max_batch candidates of
+ * up to cap slots and max_iterations <= ORBX_SIM3_MAX_ITERATIONS iterations) borrows the
+ * matcher's device and stream; the matcher must outlive it.  orbx_sim3_destroy waits for that
+ * stream; after the library's unload destructor it releases nothing. */
+#define ORBX_SIM3_MAX_ITERATIONS 4096
+#define ORBX_SIM3_STATUS_BAD_DRAW 1 /* status bit 0: a walked iteration had a draw outside [0, N - j) */
+typedef struct orbx_sim3 orbx_sim3;
+int orbx_sim3_create(orbx_matcher* m, int max_batch, int cap, int max_iterations, orbx_sim3** out);
+void orbx_sim3_destroy(orbx_sim3* s);
+
+/* The constructor (cc:37-129) and SetRansacParameters(probability, min_inliers,
+ * max_iterations) (cc:132-185) for `batch` candidates of one camera pair.
+ *   Slot i < n1 (mN1) of a candidate is kept iff mp1[i] (vpKeyFrameMP1) and mp2[i]
+ *   (vpMatched12) both lie in [0, n_mp): -1, any negative id or one outside the table skips
+ *   the slot (the caller maps NULL, isBad() and GetIndexInKeyFrame() < 0 to -1; cc:70-87).
+ *   Kept slots in slot order are the N correspondences (mvnIndices1).  mvX3Dc = Rcw Xw + tcw
+ *   per keyframe, mvP1im1 / mvP2im2 by FromCameraToImage without a depth check (cc:527),
+ *   mvnMaxError = 9.210 * level_sigma2[octave] truncated to an integer as the reference's
+ *   vector<size_t> does (Sim3Solver.h:143-144): 9, 13, 19, ... at scale 1.2; octaves are
+ *   clamped into [0, nlevels).  The iteration cap is cc:145-181 at N, evaluated by the host's
+ *   libm for every n in 0..cap and looked up on the device.  mnIterations and mnBestInliers
+ *   are reset to 0.
+ *   draws [batch][max_iterations][3] is read by the later iterate calls, indexed by the
+ *   absolute iteration, and must stay valid until the next set: draw j of an iteration is
+ *   RandomInt(0, N - 1 - j) (cc:224) and must lie in [0, N - j); otherwise that iteration has
+ *   a NaN hypothesis and 0 inliers, and ORBX_SIM3_STATUS_BAD_DRAW is set once it is walked.
+ * level_sigma2, K1 and K2 are host arrays, every other pointer is a device pointer (all are
+ * host pointers, and batch is 1, for orbx_sim3_set).  Asynchronous on `stream` (or the
+ * matcher's); the calls on one solver share its workspace, so the caller keeps them in
+ * order: one stream for a set and its iterates, or events between streams. */
+typedef struct {
+    int batch;
+    int cap;                    /* slots per candidate row, <= the solver's cap */
+    const int32_t* n1;          /* [B] mN1 = vpMatched12.size(), clamped into [0, cap] */
+    const int32_t* mp1;         /* [B][cap] vpKeyFrameMP1 as MapPoint ids */
+    const int32_t* mp2;         /* [B][cap] vpMatched12 as MapPoint ids */
+    const int32_t* oct1;        /* [B][cap] kp1.octave */
+    const int32_t* oct2;        /* [B][cap] kp2.octave */
+    int n_mp;                   /* MapPoints in the table */
+    const float* mp_pos;        /* [n_mp][3] GetWorldPos() */
+    const float* Tcw1;          /* [B][12] pKF1's pose, rows 0..2 */
+    const float* Tcw2;          /* [B][12] pKF2's pose */
+    const float* level_sigma2;  /* host: mvLevelSigma2 (nlevels), each in [0, 2^24 / 9.21) */
+    int nlevels;
+    const float* K1;            /* host: fx fy cx cy of pKF1 */
+    const float* K2;            /* host: ... of pKF2 */
+    int fix_scale;              /* mbFixScale: the scale is exactly 1 */
+    double probability;         /* in (0, 1) */
+    int min_inliers;
+    int max_iterations;         /* <= the solver's */
+    const int32_t* draws;       /* [B][max_iterations][3] */
+} orbx_sim3_batch;
+int orbx_sim3_set_batch_device(orbx_sim3* s, const orbx_sim3_batch* in, void* stream);
+
+/* iterate(n_iterations, bNoMore, vbInliers, nInliers) (cc:188-274) on every candidate of the
+ * batch in force; find() (cc:277-281) is n_iterations = max_iterations.  Per candidate, with
+ * inl_k the inlier count of absolute iteration k (err1 < thr1 && err2 < thr2, strict, cc:460):
+ * inl_k >= mnBestInliers replaces the best state (a tie goes to the later iteration), and if
+ * also inl_k > min_inliers the call returns that hypothesis: found 1, n_inliers, T12, and
+ * inliers [n1] set at mvnIndices1 (entries beyond n1 are left untouched); no_more stays 0 on
+ * that return.  Otherwise found 0, n_inliers 0, all flags 0, T12 all 0 (the empty Mat), and
+ * no_more = mnIterations >= the cap.  N < min_inliers (cc:195) or N < 3: no_more at once, no
+ * iteration.  A hypothesis whose |v| is exactly 0 (cc:371, identical point sets) is NaN, has
+ * 0 inliers, and becomes the best state while mnBestInliers is 0, as IEEE gives it.
+ *   best_R [9], best_t [3], best_s: GetEstimatedRotation / Translation / Scale (NaN before
+ *   any best state); best_inliers = mnBestInliers; best_iteration = the absolute iteration
+ *   that holds the best state, -1 if none; iterations = mnIterations after the call; n_pairs
+ *   = N; status = the ORBX_SIM3_STATUS_* bits.  Every output is a nullable device array
+ *   (host pointers to one candidate's for orbx_sim3_iterate). */
+typedef struct {
+    int32_t* found;           /* [B] */
+    int32_t* no_more;         /* [B] */
+    int32_t* n_inliers;       /* [B] */
+    uint8_t* inliers;         /* [B][cap] */
+    float* T12;               /* [B][16] */
+    float* best_R;            /* [B][9] */
+    float* best_t;            /* [B][3] */
+    float* best_s;            /* [B] */
+    int32_t* best_inliers;    /* [B] */
+    int32_t* best_iteration;  /* [B] */
+    int32_t* iterations;      /* [B] */
+    int32_t* n_pairs;         /* [B] */
+    int32_t* status;          /* [B] */
+} orbx_sim3_result;
+int orbx_sim3_iterate_device(orbx_sim3* s, int n_iterations, const orbx_sim3_result* out, void* stream);
+
+/* The single-candidate host forms: every pointer of the structs is a host pointer (batch 1;
+ * draws [max_iterations][3] is copied).  orbx_sim3_set uploads once; orbx_sim3_iterate runs
+ * the batch kernels with B = 1, synchronises once and gives the same bytes as the batch form
+ * gives that candidate.  Its wall time is the matcher's orbx_matcher_last_call_us. */
+int orbx_sim3_set(orbx_sim3* s, const orbx_sim3_batch* in);
+int orbx_sim3_iterate(orbx_sim3* s, int n_iterations, const orbx_sim3_result* out);
+
+/* The reference's draws for n correspondences: draws [iterations][3], draw j =
+ * RandomInt(0, n - 1 - j) = int(((double)rand() / ((double)RAND_MAX + 1.0)) * (n - j))
+ * (DUtils/Random.cpp:47-49) over the C library's rand(); 0, without a rand() call, where
+ * n - j <= 0.  One deviation: the draws of all iterations are taken up front, where the
+ * reference stops consuming rand() at the returning iteration.  Host only, no GPU. */
+int orbx_sim3_draws(int32_t* draws, int n, int iterations);
+
 /* Alternative kernel forms and diagnostics switches, process-wide (tests and A/B tools;
  * the product reads no environment).  Names: "pz_seg" (pyramid levels per launch, 0 = one
  * launch), "pz_byte" (byte-read k_pyramid), "desc_tiles" (tile-major describe),

@@ -394,4 +394,127 @@ private:
     int max_;
 };
 
+// Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc:37-534) on the arrays the adapter
+// extracts: vpKeyFrameMP1 / vpMatched12 as MapPoint ids into mpPos
+// (GetWorldPos(), 3 floats per id; -1 for NULL, isBad() and GetIndexInKeyFrame() < 0), the
+// octaves of kp1 / kp2 per slot, the two keyframes' poses (rows 0..2, 12 floats),
+// mvLevelSigma2 and fx fy cx cy of each.  draws: 3 per iteration (empty: the reference's, from
+// rand(), taken when SetRansacParameters runs).  Runs on the matcher's handle and stream; the
+// matcher must outlive the solver.  iterate returns T12 (16 floats, row-major; empty: the
+// reference's empty Mat).
+class Sim3Solver {
+public:
+    Sim3Solver(ORBmatcher& matcher, const std::vector<int32_t>& vpKeyFrameMP1, const std::vector<int32_t>& vpMatched12,
+               const std::vector<int32_t>& octaves1, const std::vector<int32_t>& octaves2,
+               const std::vector<float>& mpPos, const float* Tcw1, const float* Tcw2,
+               const std::vector<float>& mvLevelSigma2, const float* K1, const float* K2, bool bFixScale,
+               const std::vector<int32_t>& draws = {})
+        : m_(matcher.handle()), mp1_(vpKeyFrameMP1), mp2_(vpMatched12), oct1_(octaves1), oct2_(octaves2), pos_(mpPos),
+          sig_(mvLevelSigma2), draws_(draws), fix_(bFixScale) {
+        mN1 = (int)mp2_.size();
+        if (mp1_.size() < mp2_.size() || oct1_.size() < mp2_.size() || oct2_.size() < mp2_.size())
+            throw Error(ORBX_ERR_ARG, "Sim3Solver: one MapPoint and two octaves per slot of vpMatched12");
+        for (int i = 0; i < 12; i++) T1_[i] = Tcw1[i], T2_[i] = Tcw2[i];
+        for (int i = 0; i < 4; i++) K1_[i] = K1[i], K2_[i] = K2[i];
+        SetRansacParameters();  // cc:128
+    }
+    ~Sim3Solver() { orbx_sim3_destroy(h_); }
+    Sim3Solver(const Sim3Solver&) = delete;
+    Sim3Solver& operator=(const Sim3Solver&) = delete;
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+        if (!h_ || maxIterations > maxIts_) {
+            orbx_sim3_destroy(h_);
+            h_ = nullptr;
+            check(orbx_sim3_create(m_, 1, mN1 > 0 ? mN1 : 1, maxIterations, &h_));
+            maxIts_ = maxIterations;
+        }
+        std::vector<int32_t> d(draws_);
+        if (d.empty()) {
+            int N = 0;
+            const int n_mp = (int)(pos_.size() / 3);
+            for (int i = 0; i < mN1; i++)
+                N += mp1_[i] >= 0 && mp1_[i] < n_mp && mp2_[i] >= 0 && mp2_[i] < n_mp;
+            d.resize((size_t)maxIterations * 3);
+            check(orbx_sim3_draws(d.data(), N, maxIterations));
+        }
+        if (d.size() < (size_t)maxIterations * 3) throw Error(ORBX_ERR_ARG, "Sim3Solver: fewer draws than iterations");
+        orbx_sim3_batch in{};
+        const int32_t n1 = mN1;
+        in.batch = 1;
+        in.cap = mN1 > 0 ? mN1 : 1;
+        in.n1 = &n1;
+        const int32_t none = -1;  // mN1 == 0: the arrays are not read
+        in.mp1 = mN1 ? mp1_.data() : &none;
+        in.mp2 = mN1 ? mp2_.data() : &none;
+        in.oct1 = mN1 ? oct1_.data() : &none;
+        in.oct2 = mN1 ? oct2_.data() : &none;
+        in.n_mp = (int)(pos_.size() / 3);
+        in.mp_pos = pos_.data();
+        in.Tcw1 = T1_;
+        in.Tcw2 = T2_;
+        in.level_sigma2 = sig_.data();
+        in.nlevels = (int)sig_.size();
+        in.K1 = K1_;
+        in.K2 = K2_;
+        in.fix_scale = fix_ ? 1 : 0;
+        in.probability = probability;
+        in.min_inliers = minInliers;
+        in.max_iterations = maxIterations;
+        in.draws = d.data();
+        check(orbx_sim3_set(h_, &in));
+        its_ = maxIterations;
+    }
+
+    std::vector<float> iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+        std::vector<uint8_t> inl((size_t)(mN1 > 0 ? mN1 : 1), 0);
+        std::vector<float> T((size_t)16);
+        int32_t found = 0, no_more = 0, n = 0;
+        orbx_sim3_result out{};
+        out.found = &found;
+        out.no_more = &no_more;
+        out.n_inliers = &n;
+        out.inliers = inl.data();
+        out.T12 = T.data();
+        out.best_R = R_;
+        out.best_t = t_;
+        out.best_s = &s_;
+        out.best_inliers = &bestInliers;
+        out.best_iteration = &bestIteration;
+        out.iterations = &iterations;
+        out.n_pairs = &N;
+        out.status = &status;
+        check(orbx_sim3_iterate(h_, nIterations, &out));
+        bNoMore = no_more != 0;
+        nInliers = n;
+        vbInliers.assign((size_t)mN1, false);
+        for (int i = 0; i < mN1; i++) vbInliers[(size_t)i] = inl[(size_t)i] != 0;
+        if (!found) T.clear();
+        return T;
+    }
+    std::vector<float> find(std::vector<bool>& vbInliers12, int& nInliers) {
+        bool bFlag;
+        return iterate(its_, bFlag, vbInliers12, nInliers);  // cc:277-281
+    }
+    std::vector<float> GetEstimatedRotation() const { return std::vector<float>(R_, R_ + 9); }
+    std::vector<float> GetEstimatedTranslation() const { return std::vector<float>(t_, t_ + 3); }
+    float GetEstimatedScale() const { return s_; }
+    orbx_sim3* handle() { return h_; }
+
+    // after an iterate: mnBestInliers, the absolute iteration holding the best state (-1: none),
+    // mnIterations, N and the ORBX_SIM3_STATUS_* bits
+    int32_t bestInliers = 0, bestIteration = -1, iterations = 0, N = 0, status = 0;
+
+private:
+    orbx_matcher* m_;
+    orbx_sim3* h_ = nullptr;
+    std::vector<int32_t> mp1_, mp2_, oct1_, oct2_;
+    std::vector<float> pos_, sig_;
+    std::vector<int32_t> draws_;
+    bool fix_;
+    int mN1 = 0, maxIts_ = 0, its_ = 0;
+    float T1_[12], T2_[12], K1_[4], K2_[4];
+    float R_[9] = {}, t_[3] = {}, s_ = 0.0f;
+};
+
 }  // namespace orbx

@@ -56,6 +56,8 @@ EXPORTED = [
     "orbx_kfdb_reloc_scores", "orbx_kfdb_score_device", "orbx_kfdb_detect_relocalization_candidates_device",
     "orbx_kfdb_detect_loop_candidates_device", "orbx_kfdb_detect_relocalization_candidates",
     "orbx_kfdb_detect_loop_candidates", "orbx_pose_optimization_batch_device", "orbx_pose_optimization",
+    "orbx_sim3_create", "orbx_sim3_destroy", "orbx_sim3_set_batch_device", "orbx_sim3_iterate_device", "orbx_sim3_set",
+    "orbx_sim3_iterate", "orbx_sim3_draws",
 ]
 
 ORBX_DEPTH_U16 = 0
@@ -122,6 +124,27 @@ class PoseOptimizationBatch(C.Structure):
 
 
 ORBX_POSE_OPT_LDS_EDGES = 1984
+
+
+class Sim3Batch(C.Structure):
+    """orbx_sim3_batch."""
+    _fields_ = [("batch", C.c_int), ("cap", C.c_int), ("n1", C.c_void_p), ("mp1", C.c_void_p), ("mp2", C.c_void_p),
+                ("oct1", C.c_void_p), ("oct2", C.c_void_p), ("n_mp", C.c_int), ("mp_pos", C.c_void_p),
+                ("Tcw1", C.c_void_p), ("Tcw2", C.c_void_p), ("level_sigma2", C.POINTER(C.c_float)),
+                ("nlevels", C.c_int), ("K1", C.POINTER(C.c_float)), ("K2", C.POINTER(C.c_float)),
+                ("fix_scale", C.c_int), ("probability", C.c_double), ("min_inliers", C.c_int),
+                ("max_iterations", C.c_int), ("draws", C.c_void_p)]
+
+
+class Sim3Result(C.Structure):
+    """orbx_sim3_result."""
+    _fields_ = [(k, C.c_void_p) for k in ("found", "no_more", "n_inliers", "inliers", "T12", "best_R", "best_t",
+                                          "best_s", "best_inliers", "best_iteration", "iterations", "n_pairs",
+                                          "status")]
+
+
+ORBX_SIM3_MAX_ITERATIONS = 4096
+ORBX_SIM3_STATUS_BAD_DRAW = 1
 
 
 # ---- handle lifetime (DESIGN.md §1 "Teardown") ------------------------------------
@@ -316,6 +339,14 @@ def lib() -> C.CDLL:
     L.orbx_pose_optimization_batch_device.argtypes = [vp, C.POINTER(PoseOptimizationBatch), vp]
     L.orbx_pose_optimization.argtypes = [vp, vp, C.c_int, fp, i32p, fp, C.c_int, fp, C.c_int, C.c_float, C.c_float,
                                          C.c_float, C.c_float, C.c_float, fp, fp, u8p, ip, i32p, ip]
+    L.orbx_sim3_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.orbx_sim3_destroy.argtypes = [vp]
+    L.orbx_sim3_destroy.restype = None
+    L.orbx_sim3_set_batch_device.argtypes = [vp, C.POINTER(Sim3Batch), vp]
+    L.orbx_sim3_iterate_device.argtypes = [vp, C.c_int, C.POINTER(Sim3Result), vp]
+    L.orbx_sim3_set.argtypes = [vp, C.POINTER(Sim3Batch)]
+    L.orbx_sim3_iterate.argtypes = [vp, C.c_int, C.POINTER(Sim3Result)]
+    L.orbx_sim3_draws.argtypes = [i32p, C.c_int, C.c_int]
     L.orbx_version.restype = C.c_char_p
     L.orbx_device_count.argtypes = [ip]
     L.orbx_last_error.restype = C.c_char_p

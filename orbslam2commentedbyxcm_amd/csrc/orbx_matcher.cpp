@@ -243,6 +243,13 @@ struct orbx_matcher {
     size_t hmp_cap = 0;
 };
 
+namespace orbx {
+// for the handles that borrow a matcher's device and stream (orbx_sim3.hip)
+int matcher_device(const orbx_matcher* m) { return m->device; }
+hipStream_t matcher_stream(const orbx_matcher* m) { return m->stream; }
+void matcher_set_last_call_us(orbx_matcher* m, double us) { m->last_call_us = us; }
+}  // namespace orbx
+
 namespace {
 // Scoped: stores the enclosing host call's wall time in m->last_call_us.
 struct CallClock {
