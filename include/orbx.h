@@ -994,6 +994,74 @@ int orbx_sim3_iterate(orbx_sim3* s, int n_iterations, const orbx_sim3_result* ou
  * reference stops consuming rand() at the returning iteration.  Host only, no GPU. */
 int orbx_sim3_draws(int32_t* draws, int n, int iterations);
 
+/* ---- Optimizer::OptimizeSim3: the Sim3 refinement of loop candidates ----
+ * Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cc:
+ * 1173-1358) as LoopClosing::ComputeSim3 calls it between SearchBySim3 and the nInliers >= 20
+ * test (LoopClosing.cc:344-355), with the parts of g2o it runs (VertexSim3Expmap,
+ * EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ with g2o's numeric Jacobian, g2o::Sim3,
+ * RobustKernelHuber, the dense 7x7 LDLT, OptimizationAlgorithmLevenberg), for B candidates in
+ * HBM in one launch: one persistent workgroup per candidate runs optimize(5), the chi2 test,
+ * optimize(5 or 10) from the current estimate and the final test.  Float inputs are widened to
+ * double, everything after is double, outputs are rounded to float once.  Sums over edges have
+ * a fixed shape (no floating-point atomics): a candidate's results are the same bytes
+ * whatever the batch around it.  DESIGN.md §4.17.
+ *   Pairs, in slot order: slot i < n1 is kept iff mp1[i] and matches12[i] lie in [0, n_mp)
+ *   and idx2[i] in [0, n2) (the caller maps NULL, isBad() and GetIndexInKeyFrame() < 0 to
+ *   -1).  P3D1c = R1w mp_pos[mp1[i]] + t1w and P3D2c likewise are rounded to float as the
+ *   reference's CV_32F matrices are; obs1 = kps1[i], obs2 = kps2[idx2[i]]; information =
+ *   I * inv_level_sigma2_k[octave] of the respective keyframe (octaves clamped into
+ *   [0, nlevels)); the Huber delta is the float sqrt(th2).
+ *   matches12 is in/out: the entries of pairs rejected by either test (e12.chi2() > th2 ||
+ *   e21.chi2() > th2, in double) become -1, as vpMatches1 entries become NULL.
+ *   Outputs: R12_opt / t12_opt / s12_opt = rotation().toRotationMatrix(), translation(),
+ *   scale() of the recovered vertex; ninliers = the return value nIn; ncorr =
+ *   nCorrespondences; nbad = nBad of the first test; trace per optimisation {LM iterations
+ *   run, linear solves tried}, 0 when not run.  nCorrespondences - nBad < 10 (cc:1331):
+ *   ninliers 0, the Sim3 outputs are the inputs' bytes, the first test's rejections stay.
+ *   R12 / t12 / s12 have the layout of orbx_sim3_result.best_R / best_t / best_s.
+ * inv_level_sigma2_1 / _2, K1 and K2 are host arrays; every other pointer is a device
+ * pointer.  ninliers, ncorr, nbad and trace may be NULL.  Asynchronous on `stream` (or the
+ * matcher's). */
+typedef struct {
+    int batch;
+    int cap1;                          /* slots per candidate row */
+    const int32_t* n1;                 /* [B] vpMatches1.size(), clamped into [0, cap1] */
+    const orbx_keypoint* kps1;         /* [B][cap1] pKF1->mvKeysUn */
+    const int32_t* mp1;                /* [B][cap1] pKF1->GetMapPointMatches() as MapPoint ids */
+    int32_t* matches12;                /* [B][cap1] in/out: vpMatches1 as MapPoint ids */
+    const int32_t* idx2;               /* [B][cap1] GetIndexInKeyFrame(pKF2) of matches12[i] */
+    int cap2;
+    const int32_t* n2;                 /* [B] pKF2's keypoints, clamped into [0, cap2] */
+    const orbx_keypoint* kps2;         /* [B][cap2] pKF2->mvKeysUn */
+    int n_mp;                          /* MapPoints in the table */
+    const float* mp_pos;               /* [n_mp][3] GetWorldPos() */
+    const float* Tcw1;                 /* [B][12] pKF1's pose, rows 0..2 */
+    const float* Tcw2;                 /* [B][12] pKF2's pose */
+    const float* inv_level_sigma2_1;   /* host: pKF1->mvInvLevelSigma2 (nlevels) */
+    const float* inv_level_sigma2_2;   /* host: pKF2->mvInvLevelSigma2 (nlevels) */
+    int nlevels;
+    const float* K1;                   /* host: fx fy cx cy of pKF1 */
+    const float* K2;                   /* host: ... of pKF2 */
+    const float* R12;                  /* [B][9] */
+    const float* t12;                  /* [B][3] */
+    const float* s12;                  /* [B] */
+    float th2;
+    int fix_scale;
+    float* R12_opt;                    /* [B][9] out */
+    float* t12_opt;                    /* [B][3] out */
+    float* s12_opt;                    /* [B] out */
+    int32_t* ninliers;                 /* [B] out or NULL */
+    int32_t* ncorr;                    /* [B] out or NULL */
+    int32_t* nbad;                     /* [B] out or NULL */
+    int32_t* trace;                    /* [B][2][2] out or NULL */
+} orbx_optimize_sim3_batch;
+int orbx_optimize_sim3_batch_device(orbx_matcher* m, const orbx_optimize_sim3_batch* os, void* stream);
+
+/* The single-candidate host form: every pointer of the struct is a host pointer and batch is
+ * 1 (n1 / n2 point to one count each; cap1 >= *n1, cap2 >= *n2).  One upload, the batch kernel
+ * with B = 1, one synchronisation; the same bytes as the batch form gives that candidate. */
+int orbx_optimize_sim3(orbx_matcher* m, const orbx_optimize_sim3_batch* os);
+
 /* Alternative kernel forms and diagnostics switches, process-wide (tests and A/B tools;
  * the product reads no environment).  Names: "pz_seg" (pyramid levels per launch, 0 = one
  * launch), "pz_byte" (byte-read k_pyramid), "desc_tiles" (tile-major describe),

@@ -237,7 +237,8 @@ inline void ComputeStereoFromRGBD(const orbx_camera& cam, const std::vector<orbx
                                         mDepthMapFactor, mbf, mvKeysUn.data(), mvuRight.data(), mvDepth.data()));
 }
 
-// Optimizer (include/Optimizer.h): the one g2o call on the per-frame path.
+// Optimizer (include/Optimizer.h): the g2o call on the per-frame path and the one of
+// LoopClosing::ComputeSim3.
 // PoseOptimization(Frame*) (src/Optimizer.cc:299-502) on the Frame's arrays: mvKeysUn,
 // mvuRight (empty: monocular), mvpMapPoints as MapPoint ids (-1 = NULL) into the positions
 // mpPos (GetWorldPos(), 3 floats per id), mvInvLevelSigma2, fx fy cx cy mbf and mTcw (rows
@@ -261,6 +262,73 @@ public:
                                      out, mvbOutlier.data(), nInitialCorrespondences, trace, &inliers));
         for (int i = 0; i < 12; i++) mTcw[i] = out[i];
         return inliers;
+    }
+
+    // OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cc:1173-1358)
+    // on the keyframes' arrays: mvKeysUn1 / mvKeysUn2, pKF1's GetMapPointMatches() and
+    // vpMatches1 as MapPoint ids (-1 = NULL or isBad()) into mpPos, idx2[i] =
+    // vpMatches1[i]->GetIndexInKeyFrame(pKF2), the poses' rows 0..2, mvInvLevelSigma2 and fx fy
+    // cx cy of either keyframe.  g2oS12 is R12 (9) / t12 (3) / s12, updated in place unless 0 is
+    // returned; rejected vpMatches1 entries become -1.  Returns nIn.  trace (optional, 4 ints):
+    // per optimisation the LM iterations run and the linear solves tried.
+    static int OptimizeSim3(ORBmatcher& matcher, const std::vector<orbx_keypoint>& mvKeysUn1,
+                            const std::vector<int32_t>& vpMapPoints1, std::vector<int32_t>& vpMatches1,
+                            const std::vector<int32_t>& idx2, const std::vector<orbx_keypoint>& mvKeysUn2,
+                            const std::vector<float>& mpPos, const float* Tcw1, const float* Tcw2,
+                            const std::vector<float>& mvInvLevelSigma2_1, const std::vector<float>& mvInvLevelSigma2_2,
+                            const float* K1, const float* K2, float* R12, float* t12, float* s12, float th2,
+                            bool bFixScale, int32_t* trace = nullptr, int* nCorrespondences = nullptr,
+                            int* nBad = nullptr) {
+        const int32_t n1 = (int32_t)vpMatches1.size(), n2 = (int32_t)mvKeysUn2.size();
+        if (mvKeysUn1.size() != (size_t)n1 || vpMapPoints1.size() != (size_t)n1 || idx2.size() != (size_t)n1 ||
+            mvInvLevelSigma2_1.size() != mvInvLevelSigma2_2.size())
+            throw std::runtime_error("OptimizeSim3: array sizes differ");
+        // the call takes no null array: an empty one gets one spare element
+        const orbx_keypoint kp0{};
+        const int32_t i0 = -1;
+        int32_t m0 = -1;
+        const float p0[3] = {0.0f, 0.0f, 0.0f};
+        float Ro[9], to[3], so = 0.0f;
+        int32_t counts[3] = {0, 0, 0};
+        orbx_optimize_sim3_batch q{};
+        q.batch = 1;
+        q.cap1 = n1 > 0 ? n1 : 1;
+        q.n1 = &n1;
+        q.kps1 = n1 > 0 ? mvKeysUn1.data() : &kp0;
+        q.mp1 = n1 > 0 ? vpMapPoints1.data() : &i0;
+        q.matches12 = n1 > 0 ? vpMatches1.data() : &m0;
+        q.idx2 = n1 > 0 ? idx2.data() : &i0;
+        q.cap2 = n2 > 0 ? n2 : 1;
+        q.n2 = &n2;
+        q.kps2 = n2 > 0 ? mvKeysUn2.data() : &kp0;
+        q.n_mp = (int)(mpPos.size() / 3);
+        q.mp_pos = q.n_mp > 0 ? mpPos.data() : p0;
+        q.Tcw1 = Tcw1;
+        q.Tcw2 = Tcw2;
+        q.inv_level_sigma2_1 = mvInvLevelSigma2_1.data();
+        q.inv_level_sigma2_2 = mvInvLevelSigma2_2.data();
+        q.nlevels = (int)mvInvLevelSigma2_1.size();
+        q.K1 = K1;
+        q.K2 = K2;
+        q.R12 = R12;
+        q.t12 = t12;
+        q.s12 = s12;
+        q.th2 = th2;
+        q.fix_scale = bFixScale ? 1 : 0;
+        q.R12_opt = Ro;
+        q.t12_opt = to;
+        q.s12_opt = &so;
+        q.ninliers = &counts[0];
+        q.ncorr = &counts[1];
+        q.nbad = &counts[2];
+        q.trace = trace;
+        check(orbx_optimize_sim3(matcher.handle(), &q));
+        for (int i = 0; i < 9; i++) R12[i] = Ro[i];
+        for (int i = 0; i < 3; i++) t12[i] = to[i];
+        *s12 = so;
+        if (nCorrespondences) *nCorrespondences = counts[1];
+        if (nBad) *nBad = counts[2];
+        return counts[0];
     }
 };
 

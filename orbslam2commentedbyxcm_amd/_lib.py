@@ -57,7 +57,7 @@ EXPORTED = [
     "orbx_kfdb_detect_loop_candidates_device", "orbx_kfdb_detect_relocalization_candidates",
     "orbx_kfdb_detect_loop_candidates", "orbx_pose_optimization_batch_device", "orbx_pose_optimization",
     "orbx_sim3_create", "orbx_sim3_destroy", "orbx_sim3_set_batch_device", "orbx_sim3_iterate_device", "orbx_sim3_set",
-    "orbx_sim3_iterate", "orbx_sim3_draws",
+    "orbx_sim3_iterate", "orbx_sim3_draws", "orbx_optimize_sim3_batch_device", "orbx_optimize_sim3",
 ]
 
 ORBX_DEPTH_U16 = 0
@@ -145,6 +145,19 @@ class Sim3Result(C.Structure):
 
 ORBX_SIM3_MAX_ITERATIONS = 4096
 ORBX_SIM3_STATUS_BAD_DRAW = 1
+
+
+class OptimizeSim3Batch(C.Structure):
+    """orbx_optimize_sim3_batch."""
+    _fields_ = [("batch", C.c_int), ("cap1", C.c_int), ("n1", C.c_void_p), ("kps1", C.c_void_p), ("mp1", C.c_void_p),
+                ("matches12", C.c_void_p), ("idx2", C.c_void_p), ("cap2", C.c_int), ("n2", C.c_void_p),
+                ("kps2", C.c_void_p), ("n_mp", C.c_int), ("mp_pos", C.c_void_p), ("Tcw1", C.c_void_p),
+                ("Tcw2", C.c_void_p), ("inv_level_sigma2_1", C.POINTER(C.c_float)),
+                ("inv_level_sigma2_2", C.POINTER(C.c_float)), ("nlevels", C.c_int), ("K1", C.POINTER(C.c_float)),
+                ("K2", C.POINTER(C.c_float)), ("R12", C.c_void_p), ("t12", C.c_void_p), ("s12", C.c_void_p),
+                ("th2", C.c_float), ("fix_scale", C.c_int), ("R12_opt", C.c_void_p), ("t12_opt", C.c_void_p),
+                ("s12_opt", C.c_void_p), ("ninliers", C.c_void_p), ("ncorr", C.c_void_p), ("nbad", C.c_void_p),
+                ("trace", C.c_void_p)]
 
 
 # ---- handle lifetime (DESIGN.md §1 "Teardown") ------------------------------------
@@ -347,6 +360,8 @@ def lib() -> C.CDLL:
     L.orbx_sim3_set.argtypes = [vp, C.POINTER(Sim3Batch)]
     L.orbx_sim3_iterate.argtypes = [vp, C.c_int, C.POINTER(Sim3Result)]
     L.orbx_sim3_draws.argtypes = [i32p, C.c_int, C.c_int]
+    L.orbx_optimize_sim3_batch_device.argtypes = [vp, C.POINTER(OptimizeSim3Batch), vp]
+    L.orbx_optimize_sim3.argtypes = [vp, C.POINTER(OptimizeSim3Batch)]
     L.orbx_version.restype = C.c_char_p
     L.orbx_device_count.argtypes = [ip]
     L.orbx_last_error.restype = C.c_char_p

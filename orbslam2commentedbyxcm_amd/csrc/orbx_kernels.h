@@ -145,6 +145,44 @@ struct PoseOptArgs {
 size_t pose_opt_workspace_bytes(int batch, int cap);
 hipError_t launch_pose_opt(PoseOptArgs A, int batch, char* workspace, hipStream_t stream);
 
+// k_opt_sim3 (orbx_optsim3.hip): Optimizer::OptimizeSim3 for `batch` loop candidates, one
+// workgroup each; the pair records live in the workspace.
+struct OptSim3Args {
+    int cap1, cap2;
+    const int32_t* n1;           // [B]
+    const orbx_keypoint* kps1;   // [B][cap1]
+    const int32_t* mp1;          // [B][cap1]
+    int32_t* matches12;          // [B][cap1] in/out
+    const int32_t* idx2;         // [B][cap1]
+    const int32_t* n2;           // [B]
+    const orbx_keypoint* kps2;   // [B][cap2]
+    const float* pos;            // [n_mp][3]
+    int n_mp;
+    const float* Tcw1;           // [B][12]
+    const float* Tcw2;           // [B][12]
+    float inv_sigma2_1[ORBX_MAX_LEVELS], inv_sigma2_2[ORBX_MAX_LEVELS];
+    int nlevels;
+    float K1[4], K2[4];
+    const float* R12;            // [B][9]
+    const float* t12;            // [B][3]
+    const float* s12;            // [B]
+    float th2, delta;            // delta: the float sqrt(th2) of Optimizer.cc:1221
+    int fix_scale;
+    float* R12_opt;              // [B][9]
+    float* t12_opt;              // [B][3]
+    float* s12_opt;              // [B]
+    int32_t* ninliers;           // [B] or null
+    int32_t* ncorr;              // [B] or null
+    int32_t* nbad;               // [B] or null
+    int32_t* trace;              // [B][2][2] or null
+    double probes[14 * 8];       // set by launch_opt_sim3: Sim3(+-1e-9 e_d) as q xyzw, t, s
+    float* rec;                  // set by launch_opt_sim3
+    int32_t* eidx;
+    int32_t* active;
+};
+size_t opt_sim3_workspace_bytes(int batch, int cap1);
+hipError_t launch_opt_sim3(OptSim3Args A, int batch, char* workspace, hipStream_t stream);
+
 hipError_t launch_window_match(const uint8_t* qdesc, int nq, const uint8_t* tdesc, const int32_t* tlevel,
                                const int32_t* cand_off, const int32_t* cand, int tie_last,
                                int32_t* best_idx, int32_t* best_dist, int32_t* best_level,

@@ -2174,4 +2174,165 @@ int orbx_pose_optimization(orbx_matcher* m, const orbx_keypoint* keys, int n, co
     return ORBX_OK;
 }
 
+static const char* optimize_sim3_check(const orbx_optimize_sim3_batch* os) {
+    if (os->batch < 0 || os->cap1 <= 0 || os->cap2 <= 0 || os->n_mp < 0 || os->nlevels < 1 ||
+        os->nlevels > ORBX_MAX_LEVELS)
+        return "bad argument";
+    if (!os->inv_level_sigma2_1 || !os->inv_level_sigma2_2 || !os->K1 || !os->K2) return "null host array";
+    if (!(os->th2 >= 0.0f)) return "th2 negative or not a number";
+    if (os->batch == 0) return nullptr;
+    if (!os->n1 || !os->kps1 || !os->mp1 || !os->matches12 || !os->idx2 || !os->n2 || !os->kps2 || !os->Tcw1 ||
+        !os->Tcw2 || !os->R12 || !os->t12 || !os->s12 || !os->R12_opt || !os->t12_opt || !os->s12_opt ||
+        (os->n_mp > 0 && !os->mp_pos))
+        return "null buffer";
+    if ((size_t)os->batch * (size_t)os->cap1 >= ((size_t)1 << 31) ||
+        (size_t)os->batch * (size_t)os->cap2 >= ((size_t)1 << 31))
+        return "batch x cap of 2^31 or more";
+    return nullptr;
+}
+
+// Optimizer::OptimizeSim3 for a batch of loop candidates in HBM (see include/orbx.h)
+int orbx_optimize_sim3_batch_device(orbx_matcher* m, const orbx_optimize_sim3_batch* os, void* stream) {
+    if (!m || !os) return fail(ORBX_ERR_ARG, "null argument");
+    if (const char* why = optimize_sim3_check(os)) return fail(ORBX_ERR_ARG, why);
+    const int B = os->batch;
+    if (B == 0) return ORBX_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+    const size_t need = opt_sim3_workspace_bytes(B, os->cap1);
+    if (m->pscr_cap < need) {
+        HIP_TRY(hipStreamSynchronize(s));
+        if (m->pscr) HIP_TRY(hipFree(m->pscr));
+        m->pscr = nullptr;
+        m->pscr_cap = 0;
+        HIP_TRY(hipMalloc((void**)&m->pscr, need));
+        m->pscr_cap = need;
+    }
+    OptSim3Args A{};
+    A.cap1 = os->cap1;
+    A.cap2 = os->cap2;
+    A.n1 = os->n1;
+    A.kps1 = os->kps1;
+    A.mp1 = os->mp1;
+    A.matches12 = os->matches12;
+    A.idx2 = os->idx2;
+    A.n2 = os->n2;
+    A.kps2 = os->kps2;
+    A.pos = os->mp_pos;
+    A.n_mp = os->n_mp;
+    A.Tcw1 = os->Tcw1;
+    A.Tcw2 = os->Tcw2;
+    for (int l = 0; l < os->nlevels; l++) {
+        A.inv_sigma2_1[l] = os->inv_level_sigma2_1[l];
+        A.inv_sigma2_2[l] = os->inv_level_sigma2_2[l];
+    }
+    A.nlevels = os->nlevels;
+    for (int k = 0; k < 4; k++) {
+        A.K1[k] = os->K1[k];
+        A.K2[k] = os->K2[k];
+    }
+    A.R12 = os->R12;
+    A.t12 = os->t12;
+    A.s12 = os->s12;
+    A.th2 = os->th2;
+    A.delta = (float)std::sqrt((double)os->th2);  // Optimizer.cc:1221: const float deltaHuber = sqrt(th2)
+    A.fix_scale = os->fix_scale ? 1 : 0;
+    A.R12_opt = os->R12_opt;
+    A.t12_opt = os->t12_opt;
+    A.s12_opt = os->s12_opt;
+    A.ninliers = os->ninliers;
+    A.ncorr = os->ncorr;
+    A.nbad = os->nbad;
+    A.trace = os->trace;
+    HIP_TRY(launch_opt_sim3(A, B, m->pscr, s));
+    return ORBX_OK;
+}
+
+// The single-candidate host form: one staged candidate, the batch kernel, one synchronisation.
+int orbx_optimize_sim3(orbx_matcher* m, const orbx_optimize_sim3_batch* os) {
+    if (!m || !os) return fail(ORBX_ERR_ARG, "null argument");
+    if (os->batch != 1) return fail(ORBX_ERR_ARG, "the host form takes one candidate");
+    if (const char* why = optimize_sim3_check(os)) return fail(ORBX_ERR_ARG, why);
+    const int n1 = *os->n1, n2 = *os->n2;
+    if (n1 < 0 || n1 > os->cap1 || n2 < 0 || n2 > os->cap2) return fail(ORBX_ERR_ARG, "count outside [0, cap]");
+    CallClock clock(m);
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    const size_t c1 = (size_t)(n1 > 0 ? n1 : 1), c2 = (size_t)(n2 > 0 ? n2 : 1);
+    const size_t nt = (size_t)(os->n_mp > 0 ? os->n_mp : 1);
+    // inputs: kps1, mp1, idx2, kps2, mp_pos, one block {Tcw1, Tcw2, R12, t12, s12, n1, n2}; then
+    // the outputs as one block: R12_opt [9], t12_opt [3], s12_opt, ninliers, ncorr, nbad,
+    // trace [4], matches12 [c1]
+    const size_t o_k1 = 0, o_mp1 = o_k1 + pad(sizeof(orbx_keypoint) * c1), o_i2 = o_mp1 + pad(4 * c1),
+                 o_k2 = o_i2 + pad(4 * c1), o_pos = o_k2 + pad(sizeof(orbx_keypoint) * c2), o_in = o_pos + pad(12 * nt),
+                 o_out = o_in + pad(40 * 4), out_bytes = 20 * 4 + 4 * c1, total = o_out + pad(out_bytes);
+    if (m->pstage_cap < total) {
+        HIP_TRY(hipStreamSynchronize(s));
+        if (m->pstage) HIP_TRY(hipFree(m->pstage));
+        m->pstage = nullptr;
+        m->pstage_cap = 0;
+        HIP_TRY(hipMalloc((void**)&m->pstage, total));
+        m->pstage_cap = total;
+    }
+    char* p = m->pstage;
+    if (n1 > 0) {
+        HIP_TRY(hipMemcpyAsync(p + o_k1, os->kps1, sizeof(orbx_keypoint) * n1, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p + o_mp1, os->mp1, 4 * (size_t)n1, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p + o_i2, os->idx2, 4 * (size_t)n1, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p + o_out + 80, os->matches12, 4 * (size_t)n1, hipMemcpyHostToDevice, s));
+    }
+    if (n2 > 0) HIP_TRY(hipMemcpyAsync(p + o_k2, os->kps2, sizeof(orbx_keypoint) * n2, hipMemcpyHostToDevice, s));
+    if (os->n_mp > 0) HIP_TRY(hipMemcpyAsync(p + o_pos, os->mp_pos, 12 * (size_t)os->n_mp, hipMemcpyHostToDevice, s));
+    int32_t in[40] = {};
+    std::memcpy(in, os->Tcw1, 48);
+    std::memcpy(in + 12, os->Tcw2, 48);
+    std::memcpy(in + 24, os->R12, 36);
+    std::memcpy(in + 33, os->t12, 12);
+    std::memcpy(in + 36, os->s12, 4);
+    in[37] = n1;
+    in[38] = n2;
+    HIP_TRY(hipMemcpyAsync(p + o_in, in, sizeof(in), hipMemcpyHostToDevice, s));
+    orbx_optimize_sim3_batch d = *os;
+    d.cap1 = (int)c1;
+    d.cap2 = (int)c2;
+    d.kps1 = (const orbx_keypoint*)(p + o_k1);
+    d.mp1 = (const int32_t*)(p + o_mp1);
+    d.idx2 = (const int32_t*)(p + o_i2);
+    d.kps2 = (const orbx_keypoint*)(p + o_k2);
+    d.mp_pos = (const float*)(p + o_pos);
+    const float* fin = (const float*)(p + o_in);
+    d.Tcw1 = fin;
+    d.Tcw2 = fin + 12;
+    d.R12 = fin + 24;
+    d.t12 = fin + 33;
+    d.s12 = fin + 36;
+    d.n1 = (const int32_t*)(p + o_in) + 37;
+    d.n2 = (const int32_t*)(p + o_in) + 38;
+    float* fout = (float*)(p + o_out);
+    d.R12_opt = fout;
+    d.t12_opt = fout + 9;
+    d.s12_opt = fout + 12;
+    d.ninliers = (int32_t*)(p + o_out) + 13;
+    d.ncorr = (int32_t*)(p + o_out) + 14;
+    d.nbad = (int32_t*)(p + o_out) + 15;
+    d.trace = (int32_t*)(p + o_out) + 16;
+    d.matches12 = (int32_t*)(p + o_out) + 20;
+    const int rc = orbx_optimize_sim3_batch_device(m, &d, s);
+    if (rc) return rc;
+    std::vector<char> h(out_bytes);
+    HIP_TRY(hipMemcpyAsync(h.data(), p + o_out, out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::memcpy(os->R12_opt, h.data(), 36);
+    std::memcpy(os->t12_opt, h.data() + 36, 12);
+    std::memcpy(os->s12_opt, h.data() + 48, 4);
+    int32_t c[7];
+    std::memcpy(c, h.data() + 52, 28);
+    if (os->ninliers) *os->ninliers = c[0];
+    if (os->ncorr) *os->ncorr = c[1];
+    if (os->nbad) *os->nbad = c[2];
+    if (os->trace) std::memcpy(os->trace, c + 3, 16);
+    if (n1 > 0) std::memcpy(os->matches12, h.data() + 80, 4 * (size_t)n1);
+    return ORBX_OK;
+}
+
 }  // extern "C"

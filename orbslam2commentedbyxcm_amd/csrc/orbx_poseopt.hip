@@ -34,6 +34,7 @@
 
 #include "orbx.h"
 #include "orbx_kernels.h"
+#include "orbx_lm.h"
 
 namespace orbx {
 
@@ -43,6 +44,10 @@ constexpr int kPoThreads = 256;
 constexpr int kPoWaves = kPoThreads / 64;
 constexpr int kRecWords = 8;  // Xw[3], u, v, u_right, invSigma2, flags
 constexpr int kFlagStereo = 1, kFlagOutlier = 2;
+
+using lm::huber;
+using lm::quat_from_matrix;
+using lm::quat_rotate;
 
 struct Pose {
     double qx, qy, qz, qw, tx, ty, tz;
@@ -68,52 +73,6 @@ __device__ __forceinline__ void quat_normalize(double& x, double& y, double& z, 
     w = w / n;
 }
 
-// Eigen::Quaterniond(Matrix3d)
-__device__ __forceinline__ void quat_from_matrix(const double (&m)[3][3], double (&q)[4]) {
-    double t = m[0][0] + m[1][1] + m[2][2];
-    if (t > 0.0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (m[2][1] - m[1][2]) * t;
-        q[1] = (m[0][2] - m[2][0]) * t;
-        q[2] = (m[1][0] - m[0][1]) * t;
-    } else if (m[0][0] >= m[1][1] && m[0][0] >= m[2][2]) {  // i = 0 (the first largest diagonal entry)
-        t = sqrt(m[0][0] - m[1][1] - m[2][2] + 1.0);
-        q[0] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (m[2][1] - m[1][2]) * t;
-        q[1] = (m[1][0] + m[0][1]) * t;
-        q[2] = (m[2][0] + m[0][2]) * t;
-    } else if (m[1][1] >= m[2][2]) {  // i = 1
-        t = sqrt(m[1][1] - m[2][2] - m[0][0] + 1.0);
-        q[1] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (m[0][2] - m[2][0]) * t;
-        q[2] = (m[2][1] + m[1][2]) * t;
-        q[0] = (m[0][1] + m[1][0]) * t;
-    } else {  // i = 2
-        t = sqrt(m[2][2] - m[0][0] - m[1][1] + 1.0);
-        q[2] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (m[1][0] - m[0][1]) * t;
-        q[0] = (m[0][2] + m[2][0]) * t;
-        q[1] = (m[1][2] + m[2][1]) * t;
-    }
-}
-
-// Eigen's Quaternion * Vector3 (uv = 2 q.vec x v; v + w uv + q.vec x uv)
-__device__ __forceinline__ void quat_rotate(double qx, double qy, double qz, double qw, double X, double Y, double Z,
-                                            double& x, double& y, double& z) {
-    double ux = qy * Z - qz * Y, uy = qz * X - qx * Z, uz = qx * Y - qy * X;
-    ux += ux;
-    uy += uy;
-    uz += uz;
-    x = X + qw * ux + (qy * uz - qz * uy);
-    y = Y + qw * uy + (qz * ux - qx * uz);
-    z = Z + qw * uz + (qx * uy - qy * ux);
-}
-
 // SE3Quat::map, se3quat.h:217-220
 __device__ __forceinline__ void pose_map(const Pose& P, double X, double Y, double Z, double& x, double& y,
                                          double& z) {
@@ -125,19 +84,7 @@ __device__ __forceinline__ void pose_map(const Pose& P, double X, double Y, doub
 
 // Eigen's toRotationMatrix
 __device__ __forceinline__ void quat_to_matrix(const Pose& P, double (&R)[3][3]) {
-    const double tx = 2.0 * P.qx, ty = 2.0 * P.qy, tz = 2.0 * P.qz;
-    const double twx = tx * P.qw, twy = ty * P.qw, twz = tz * P.qw;
-    const double txx = tx * P.qx, txy = ty * P.qx, txz = tz * P.qx;
-    const double tyy = ty * P.qy, tyz = tz * P.qy, tzz = tz * P.qz;
-    R[0][0] = 1.0 - (tyy + tzz);
-    R[0][1] = txy - twz;
-    R[0][2] = txz + twy;
-    R[1][0] = txy + twz;
-    R[1][1] = 1.0 - (txx + tzz);
-    R[1][2] = tyz - twx;
-    R[2][0] = txz - twy;
-    R[2][1] = tyz + twx;
-    R[2][2] = 1.0 - (txx + tyy);
+    lm::quat_to_matrix(P.qx, P.qy, P.qz, P.qw, R);
 }
 
 // SE3Quat::exp(x) * P: types_six_dof_expmap.h:73-76 with se3quat.h:223-257 and 104-110
@@ -233,76 +180,6 @@ __device__ __forceinline__ double edge_error(const Edge& E, const Pose& P, const
     return chi2;
 }
 
-// RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91): rho(e) returned, rho'(e) in rho1.
-__device__ __forceinline__ double huber(double chi2, double delta, bool robust, double& rho1) {
-    rho1 = 1.0;
-    if (!robust) return chi2;
-    const double dsqr = delta * delta;
-    if (chi2 > dsqr) {
-        const double sq = sqrt(chi2);
-        rho1 = delta / sq;
-        return 2.0 * sq * delta - dsqr;
-    }
-    return chi2;
-}
-
-// All threads leave with the same sums: lanes by butterfly, waves in wave order.
-template <int N>
-__device__ __forceinline__ void block_sum(double (&v)[N], double* s_red) {
-#pragma unroll
-    for (int k = 0; k < N; k++)
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) v[k] += __shfl_xor(v[k], m, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < N; k++) s_red[wave * N + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        double s = s_red[k];
-#pragma unroll
-        for (int w = 1; w < kPoWaves; w++) s += s_red[w * N + k];
-        v[k] = s;
-    }
-    __syncthreads();
-}
-
-// The same order, the sums left in LDS (s_sum [N]) for every thread to read.
-template <int N>
-__device__ __forceinline__ void block_sum_lds(double (&v)[N], double* s_red, double* s_sum) {
-#pragma unroll
-    for (int k = 0; k < N; k++)
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) v[k] += __shfl_xor(v[k], m, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < N; k++) s_red[wave * N + k] = v[k];
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < N; k += kPoThreads) {
-        double s = s_red[k];
-#pragma unroll
-        for (int w = 1; w < kPoWaves; w++) s += s_red[w * N + k];
-        s_sum[k] = s;
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ int block_sum_int(int v, int* s_cnt) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < kPoWaves; w++) s += s_cnt[w];
-    __syncthreads();
-    return s;
-}
-
 // computeActiveErrors + activeRobustChi2 + buildSystem over the active (level 0) edges:
 // s_sum[0..20] the upper triangle of H row by row, s_sum[21..26] = -b, s_sum[27] = chi.
 __device__ __forceinline__ void linearize(const float* rec, int stride, int ne, const Pose& P, const Cam& C,
@@ -361,7 +238,7 @@ __device__ __forceinline__ void linearize(const float* rec, int stride, int ne, 
             }
         }
     }
-    block_sum_lds<28>(v, s_red, s_sum);
+    lm::block_sum_lds<28, kPoWaves>(v, s_red, s_sum);
 }
 
 // computeActiveErrors + activeRobustChi2 at a trial pose
@@ -375,55 +252,8 @@ __device__ __forceinline__ double robust_chi(const float* rec, int stride, int n
         const double chi2 = edge_error(E, P, C, err, x, y, z);
         v[0] += huber(chi2, (E.flags & kFlagStereo) ? C.delta_stereo : C.delta_mono, robust, rho1);
     }
-    block_sum<1>(v, s_red);
+    lm::block_sum<1, kPoWaves>(v, s_red);
     return v[0];
-}
-
-// (H + lambda I) x = b by a dense LDL^T without pivoting.  A pivot that is not positive (or
-// not finite) is a failed solve (linear_solver_dense.h:107-112) and leaves x as it was.
-__device__ __forceinline__ bool ldlt_solve(const double* h, double lam, const double (&b)[6], double (&x)[6]) {
-    double A[6][6], L[6][6], d[6], y[6];
-    {
-        int k = 0;
-#pragma unroll
-        for (int r = 0; r < 6; r++)
-#pragma unroll
-            for (int c = r; c < 6; c++, k++) A[r][c] = A[c][r] = h[k];
-    }
-#pragma unroll
-    for (int j = 0; j < 6; j++) A[j][j] = A[j][j] + lam;
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double s = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) s = s - L[j][k] * L[j][k] * d[k];
-        if (!(s > 0.0) || !isfinite(s)) ok = false;
-        d[j] = s;
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-            double t = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; k++) t = t - L[i][k] * L[j][k] * d[k];
-            L[i][j] = t / s;
-        }
-    }
-    if (!ok) return false;
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double t = b[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) t = t - L[i][k] * y[k];
-        y[i] = t;
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double t = y[i] / d[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; k++) t = t - L[k][i] * x[k];
-        x[i] = t;
-    }
-    return true;
 }
 
 // The four rounds (Optimizer.cc:440-493) over the frame's records at rec (LDS or the
@@ -463,7 +293,7 @@ __device__ __forceinline__ int optimize_frame(float* rec, int stride, int ne, co
                 int qmax = 0;
                 double rho = 0.0;
                 do {
-                    const bool ok = ldlt_solve(h, lam, b, x);
+                    const bool ok = lm::ldlt_solve<6>(h, lam, b, x);
                     const Pose trial = pose_update(x, cur);
                     double temp = robust_chi(rec, stride, ne, trial, C, robust, s_red);
                     errp = trial;
@@ -513,7 +343,7 @@ __device__ __forceinline__ int optimize_frame(float* rec, int stride, int ne, co
             rec[7 * stride + e] = __int_as_float((E.flags & kFlagStereo) | (out ? kFlagOutlier : 0));
             bad += out;
         }
-        nbad_edges = block_sum_int(bad, s_cnt);
+        nbad_edges = lm::block_sum_int<kPoWaves>(bad, s_cnt);
         P = cur;
         if (ne < 10) break;  // cc:491
     }
@@ -653,7 +483,7 @@ __global__ __launch_bounds__(kPoThreads) void k_pose_opt(PoseOptArgs A) {
         }
     }
     if (A.nmatches_map) {
-        nmap = block_sum_int(nmap, s_cnt);
+        nmap = lm::block_sum_int<kPoWaves>(nmap, s_cnt);
         if (tid == 0) A.nmatches_map[b] = nmap;
     }
 }

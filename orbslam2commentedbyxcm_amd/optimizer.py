@@ -1,9 +1,12 @@
-"""Optimizer::PoseOptimization on the GPU (include/orbx.h, csrc/orbx_poseopt.hip).
+"""Optimizer::PoseOptimization and Optimizer::OptimizeSim3 on the GPU (include/orbx.h,
+csrc/orbx_poseopt.hip, csrc/orbx_optsim3.hip).
 
 PoseOptimizer mirrors the one g2o call on ORB-SLAM2's per-frame path
 (src/Optimizer.cc:299-502): PoseOptimization for one frame on host arrays, and
 pose_optimization_batch_device for B frames in HBM with the callers' epilogue
-(Tracking.cc:1004-1017).
+(Tracking.cc:1004-1017).  Sim3Optimizer mirrors the one of LoopClosing::ComputeSim3
+(src/Optimizer.cc:1173-1358): OptimizeSim3 for one loop candidate on host arrays, and
+optimize_sim3_batch_device for B candidates in HBM.
 """
 from __future__ import annotations
 
@@ -141,3 +144,131 @@ class PoseOptStage:
 
     def results(self, k: int) -> dict:
         return dict(self.buf[k])
+
+
+class Sim3Optimizer:
+    """Optimizer::OptimizeSim3 (src/Optimizer.cc:1173-1358) on the GPU (csrc/orbx_optsim3.hip):
+    OptimizeSim3 for one loop candidate on host arrays and optimize_sim3_batch_device for B
+    candidates in HBM, fed by Sim3Solver's best_R / best_t / best_s and SearchBySim3's
+    matches.  Owns its library handle or borrows an ORBmatcher's, as PoseOptimizer does."""
+
+    def __init__(self, device: int = 0, matcher=None):
+        self._h = None
+        self._own = matcher is None
+        self._matcher = matcher
+        if matcher is not None:
+            self.device = matcher.device
+            self._h = matcher._h
+            return
+        self.device = int(device)
+        h = C.c_void_p()
+        L.check(L.lib().orbx_matcher_create(self.device, 0.6, 1, C.byref(h)))
+        self._destroy = L.lib().orbx_matcher_destroy  # held: module globals may be gone at exit
+        self._h = h
+        L.track(self)
+
+    def close(self) -> None:
+        """Release the handle (waits for its stream); idempotent.  A borrowed one is left alone."""
+        if getattr(self, "_h", None) and self._own:
+            self._destroy(self._h)
+        self._h = None
+
+    def __del__(self, _finalizing=sys.is_finalizing):
+        if not _finalizing():
+            self.close()
+
+    def last_call_us(self) -> float:
+        return float(L.lib().orbx_matcher_last_call_us(self._h))
+
+    def OptimizeSim3(self, keys_un1, mp1, matches12, idx2, keys_un2, mp_pos, Tcw1, Tcw2, inv_level_sigma2_1,
+                     inv_level_sigma2_2, K1, K2, R12, t12, s12, th2, fix_scale) -> dict:
+        """Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) on host arrays:
+        keys_un1 (n1,) / keys_un2 (n2,) KEYPOINT_DTYPE (mvKeysUn), mp1 (n1,) pKF1's MapPoint ids,
+        matches12 (n1,) vpMatches1 as MapPoint ids, idx2 (n1,) GetIndexInKeyFrame(pKF2), mp_pos
+        (n_mp, 3) f32, Tcw1 / Tcw2 12 floats, K1 / K2 = fx fy cx cy, S12 as R12 (9) t12 (3) s12.
+        Returns R12, t12, s12 (f32), matches12 (rejected entries -1), ninliers (the return
+        value), ncorr, nbad and trace (2, 2) i32."""
+        k1 = np.ascontiguousarray(keys_un1, dtype=L.KEYPOINT_DTYPE)
+        k2 = np.ascontiguousarray(keys_un2, dtype=L.KEYPOINT_DTYPE)
+        n1, n2 = len(k1), len(k2)
+        m1 = np.ascontiguousarray(mp1, dtype=np.int32)
+        m12 = np.array(matches12, dtype=np.int32, copy=True)
+        i2 = np.ascontiguousarray(idx2, dtype=np.int32)
+        if not (len(m1) == len(m12) == len(i2) == n1):
+            raise ValueError("keys_un1, mp1, matches12 and idx2 must have one length")
+
+        def room(a, dtype):  # the call takes no null array: an empty one gets one spare element
+            return a if len(a) else np.zeros(1, dtype)
+
+        k1, k2 = room(k1, L.KEYPOINT_DTYPE), room(k2, L.KEYPOINT_DTYPE)
+        m1, m12, i2 = room(m1, np.int32), room(m12, np.int32), room(i2, np.int32)
+        pos = _f32(mp_pos).reshape(-1, 3)
+        t1, t2 = _f32(Tcw1).reshape(-1), _f32(Tcw2).reshape(-1)
+        sig1, sig2 = _f32(inv_level_sigma2_1), _f32(inv_level_sigma2_2)
+        kk1, kk2 = _f32(K1).reshape(-1), _f32(K2).reshape(-1)
+        R, t, s = _f32(R12).reshape(-1), _f32(t12).reshape(-1), _f32([s12]).reshape(-1)
+        if len(t1) != 12 or len(t2) != 12 or len(kk1) != 4 or len(kk2) != 4 or len(R) != 9 or len(t) != 3:
+            raise ValueError("Tcw 12, K 4, R12 9 and t12 3 entries")
+        if len(sig1) != len(sig2):
+            raise ValueError("both keyframes need one number of levels")
+        cn1, cn2 = np.array([n1], np.int32), np.array([n2], np.int32)
+        Ro, to, so = np.empty(9, np.float32), np.empty(3, np.float32), np.empty(1, np.float32)
+        cnt = np.zeros(3, np.int32)
+        trace = np.zeros((2, 2), np.int32)
+        vp = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+        q = L.OptimizeSim3Batch()
+        q.batch, q.cap1, q.cap2 = 1, max(n1, 1), max(n2, 1)
+        q.n1, q.kps1, q.mp1, q.matches12, q.idx2 = vp(cn1), vp(k1), vp(m1), vp(m12), vp(i2)
+        q.n2, q.kps2 = vp(cn2), vp(k2)
+        q.n_mp, q.mp_pos = len(pos), vp(pos) if len(pos) else None
+        q.Tcw1, q.Tcw2 = vp(t1), vp(t2)
+        q.inv_level_sigma2_1, q.inv_level_sigma2_2, q.nlevels = sig1.ctypes.data_as(F32P), sig2.ctypes.data_as(F32P), len(sig1)
+        q.K1, q.K2 = kk1.ctypes.data_as(F32P), kk2.ctypes.data_as(F32P)
+        q.R12, q.t12, q.s12 = vp(R), vp(t), vp(s)
+        q.th2, q.fix_scale = float(th2), 1 if fix_scale else 0
+        q.R12_opt, q.t12_opt, q.s12_opt = vp(Ro), vp(to), vp(so)
+        q.ninliers, q.ncorr, q.nbad = vp(cnt[0:1]), vp(cnt[1:2]), vp(cnt[2:3])
+        q.trace = vp(trace)
+        L.check(L.lib().orbx_optimize_sim3(self._h, C.byref(q)))
+        return dict(R12=Ro, t12=to, s12=so[0], matches12=m12[:n1], ninliers=int(cnt[0]), ncorr=int(cnt[1]),
+                    nbad=int(cnt[2]), trace=trace)
+
+    def optimize_sim3_batch_device(self, d_kps1, d_n1, d_mp1, d_matches12, d_idx2, d_kps2, d_n2, d_mp_pos, d_Tcw1,
+                                   d_Tcw2, inv_level_sigma2_1, inv_level_sigma2_2, K1, K2, d_R12, d_t12, d_s12, th2,
+                                   fix_scale, d_R12_opt, d_t12_opt, d_s12_opt, d_ninliers=None, d_ncorr=None,
+                                   d_nbad=None, d_trace=None, cap2=None, stream=None) -> None:
+        """orbx_optimize_sim3_batch_device on device tensors: d_kps1 (B, cap1) / d_kps2 (B, cap2)
+        keypoints (any 28-byte layout), d_n1 / d_n2 (B,) i32, d_mp1 / d_matches12 (in/out) /
+        d_idx2 (B, cap1) i32, d_mp_pos (n_mp, 3) f32, d_Tcw1 / d_Tcw2 (B, 12), d_R12 (B, 9),
+        d_t12 (B, 3), d_s12 (B,) f32 -- Sim3Solver's best_R / best_t / best_s as they are --
+        and the outputs of the same shapes; optional d_ninliers / d_ncorr / d_nbad (B,) and
+        d_trace (B, 2, 2) i32.  cap2: keypoints per row of d_kps2 when its shape does not say (a
+        byte tensor is taken as 28 bytes per keypoint).  Asynchronous on `stream` (or the handle's)."""
+        B, cap1 = d_mp1.shape[0], d_mp1.shape[1]
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        sig1, sig2 = _f32(inv_level_sigma2_1), _f32(inv_level_sigma2_2)
+        if len(sig1) != len(sig2):
+            raise ValueError("both keyframes need one number of levels")
+        kk1, kk2 = _f32(K1).reshape(-1), _f32(K2).reshape(-1)
+        if len(kk1) != 4 or len(kk2) != 4:
+            raise ValueError("K1 and K2 are fx fy cx cy")
+        q = L.OptimizeSim3Batch()
+        q.batch, q.cap1, q.cap2 = B, cap1, self._cap2(d_kps2) if cap2 is None else int(cap2)
+        q.n1, q.kps1, q.mp1, q.matches12, q.idx2 = ptr(d_n1), ptr(d_kps1), ptr(d_mp1), ptr(d_matches12), ptr(d_idx2)
+        q.n2, q.kps2 = ptr(d_n2), ptr(d_kps2)
+        q.n_mp, q.mp_pos = int(d_mp_pos.shape[0]), ptr(d_mp_pos)
+        q.Tcw1, q.Tcw2 = ptr(d_Tcw1), ptr(d_Tcw2)
+        q.inv_level_sigma2_1, q.inv_level_sigma2_2, q.nlevels = sig1.ctypes.data_as(F32P), sig2.ctypes.data_as(F32P), len(sig1)
+        q.K1, q.K2 = kk1.ctypes.data_as(F32P), kk2.ctypes.data_as(F32P)
+        q.R12, q.t12, q.s12 = ptr(d_R12), ptr(d_t12), ptr(d_s12)
+        q.th2, q.fix_scale = float(th2), 1 if fix_scale else 0
+        q.R12_opt, q.t12_opt, q.s12_opt = ptr(d_R12_opt), ptr(d_t12_opt), ptr(d_s12_opt)
+        q.ninliers, q.ncorr, q.nbad, q.trace = ptr(d_ninliers), ptr(d_ncorr), ptr(d_nbad), ptr(d_trace)
+        s = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        L.check(L.lib().orbx_optimize_sim3_batch_device(self._h, C.byref(q), s))
+
+    @staticmethod
+    def _cap2(d_kps2) -> int:
+        """Keypoints per row of a (B, cap2) structured or (B, cap2 * 28) byte tensor."""
+        cols = int(d_kps2.shape[1])
+        return cols // 28 if d_kps2.element_size() == 1 else cols
