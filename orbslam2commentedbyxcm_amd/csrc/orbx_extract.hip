@@ -512,19 +512,24 @@ __global__ __launch_bounds__(256) void k_level_tiles(const uint8_t* __restrict__
     int l = 0;
     while (l + 1 < L && tile >= lv[l + 1].tile_first) l++;
     const LevelGeom& g = lv[l];
+    // the level's size and pitch, held in scalar registers from here on: read through g
+    // they are loaded again inside the branches and loops below, a scalar-load round trip
+    // each time
+    const int gw = __builtin_amdgcn_readfirstlane(g.w), gh = __builtin_amdgcn_readfirstlane(g.h);
+    const int gpitch = __builtin_amdgcn_readfirstlane(g.pitch);
     const int t = tile - g.tile_first;
     const int ty = t / g.tiles_x;
     const int X0 = (t - ty * g.tiles_x) * kTW, Y0 = ty * kTH;
     // level 0 from the input frame itself when it is read in place (l0 != null)
     const bool in0 = l == 0 && l0 != nullptr;
     const uint8_t* img = in0 ? l0 + (size_t)f * l0_fp : pyr + (size_t)f * fb + g.off;
-    const int ipitch = in0 ? l0_pitch : g.pitch;
+    const int ipitch = in0 ? l0_pitch : gpitch;
     // ---- stage rows Y0-3 .. Y0+kTH+2, columns X0-16 .. X0+79 (REFLECT_101 at the ROI
     // edges) as 16-byte loads (pitch and level offsets are multiples of 64); all loads
     // of a thread are issued before the LDS stores: no per-load round trip
     {
         constexpr int kRow = (kTW + 2 * kSX) / kLU, kN = (kTH + 6) * kRow, kPer = (kN + 255) / 256;
-        const bool edge = !(X0 >= kSX && X0 + kTW + kSX <= g.w);
+        const bool edge = !(X0 >= kSX && X0 + kTW + kSX <= gw);
         lt_load_t v[kPer];
 #pragma unroll
         for (int k = 0; k < kPer; k++) {
@@ -533,7 +538,7 @@ __global__ __launch_bounds__(256) void k_level_tiles(const uint8_t* __restrict__
             // edge tile: the start column clamped into the row (a load holding an in-range
             // column never clamps: X0 and pitch are multiples of 64)
             const int col = edge ? min(max(X0 - kSX + kLU * cu, 0), ipitch - kLU) : X0 - kSX + kLU * cu;
-            v[k] = *(const lt_load_t*)(img + (size_t)reflect101(Y0 + r - 3, g.h) * ipitch + col);
+            v[k] = *(const lt_load_t*)(img + (size_t)reflect101(Y0 + r - 3, gh) * ipitch + col);
         }
 #pragma unroll
         for (int k = 0; k < kPer; k++) {
@@ -547,8 +552,8 @@ __global__ __launch_bounds__(256) void k_level_tiles(const uint8_t* __restrict__
             __syncthreads();
             for (int i = tid; i < (kTH + 6) * 6; i += 256) {
                 const int r = i / 6, k = i - 6 * r;
-                const int col = k < 3 ? -1 - k : g.w + k - 3;  // REFLECT_101 source: -col or 2w - 2 - col
-                const int sc = col - X0 + kSX, ss = (k < 3 ? -col : 2 * g.w - 2 - col) - X0 + kSX;
+                const int col = k < 3 ? -1 - k : gw + k - 3;  // REFLECT_101 source: -col or 2w - 2 - col
+                const int sc = col - X0 + kSX, ss = (k < 3 ? -col : 2 * gw - 2 - col) - X0 + kSX;
                 if (sc >= 0 && sc < kSW) s_in[r][sc] = s_in[r][ss];
             }
         }
@@ -561,39 +566,39 @@ __global__ __launch_bounds__(256) void k_level_tiles(const uint8_t* __restrict__
     // its detection-area column mask is computed once.
     {
         const int j = tid & 15, c0 = kSX + 4 * j, x0 = X0 + 4 * j;
-        unsigned colmask = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) colmask |= (x0 + k >= kEdge && x0 + k < g.w - kEdge) ? 1u << k : 0u;
+        // bits k with x0 + k in [kEdge, w - kEdge), branch-free
+        const int klo = min(max(kEdge - x0, 0), 4), khi = min(max(gw - kEdge - x0, 0), 4);
+        const unsigned colmask = ((1u << khi) - 1u) & ~((1u << klo) - 1u);
         const short2_t tq1 = {(short)(tq + 1), (short)(tq + 1)};
         unsigned pass = 0;  // bit 4 it + k: pixel (row tid/16 + 16 it, column 4j + k) passes
 #pragma unroll
         for (int it = 0; it < kTH / 16; it++) {
             const int r = (tid >> 4) + 16 * it;
             const int y = Y0 + r;
-            if (colmask != 0 && y >= kEdge && y < g.h - kEdge) {
+            if (colmask != 0 && (unsigned)(y - kEdge) < (unsigned)max(gh - 2 * kEdge, 0)) {
                 const uint32_t* rc = (const uint32_t*)&s_in[r + 3][c0];
-                const uint32_t V = rc[0];
+                const uint32_t rlo = rc[-1], V = rc[0], rhi = rc[1];
                 const uint32_t C0 = *(const uint32_t*)&s_in[r + 6][c0];  // ring 0  (0, +3)
                 const uint32_t C8 = *(const uint32_t*)&s_in[r][c0];      // ring 8  (0, -3)
-                const uint32_t C4 = row_bytes(rc[-1], rc[0], rc[1], 3);   // ring 4  (+3, 0)
-                const uint32_t C12 = row_bytes(rc[-1], rc[0], rc[1], -3); // ring 12 (-3, 0)
+                const uint32_t C4 = row_bytes(rlo, V, rhi, 3);           // ring 4  (+3, 0)
+                const uint32_t C12 = row_bytes(rlo, V, rhi, -3);         // ring 12 (-3, 0)
                 uint32_t q[2];
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
                     const short2_t v = __builtin_bit_cast(short2_t, h ? hi_pair(V) : lo_pair(V));
-                    const short2_t a0 = __builtin_bit_cast(short2_t, h ? hi_pair(C0) : lo_pair(C0)) - v;
-                    const short2_t a4 = __builtin_bit_cast(short2_t, h ? hi_pair(C4) : lo_pair(C4)) - v;
-                    const short2_t a8 = __builtin_bit_cast(short2_t, h ? hi_pair(C8) : lo_pair(C8)) - v;
-                    const short2_t a12 = __builtin_bit_cast(short2_t, h ? hi_pair(C12) : lo_pair(C12)) - v;
-                    // bright: min of an adjacent pair of (x - v); dark: min of (v - x) = -max(x - v)
-                    const short2_t br = __builtin_elementwise_max(
-                        __builtin_elementwise_max(__builtin_elementwise_min(a0, a4), __builtin_elementwise_min(a4, a8)),
-                        __builtin_elementwise_max(__builtin_elementwise_min(a8, a12), __builtin_elementwise_min(a12, a0)));
-                    const short2_t dk = __builtin_elementwise_min(
-                        __builtin_elementwise_min(__builtin_elementwise_max(a0, a4), __builtin_elementwise_max(a4, a8)),
-                        __builtin_elementwise_min(__builtin_elementwise_max(a8, a12), __builtin_elementwise_max(a12, a0)));
-                    // max(br, -dk) - (tq + 1) >= 0 <=> the pixel passes; sign in bits 15 / 31
-                    q[h] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(br, short2_t{0, 0} - dk) - tq1);
+                    const short2_t p0 = __builtin_bit_cast(short2_t, h ? hi_pair(C0) : lo_pair(C0));
+                    const short2_t p4 = __builtin_bit_cast(short2_t, h ? hi_pair(C4) : lo_pair(C4));
+                    const short2_t p8 = __builtin_bit_cast(short2_t, h ? hi_pair(C8) : lo_pair(C8));
+                    const short2_t p12 = __builtin_bit_cast(short2_t, h ? hi_pair(C12) : lo_pair(C12));
+                    // every adjacent pair is one vertical x one horizontal point, so the best
+                    // bright pair min is min(max(p0, p8), max(p4, p12)) and the best dark pair
+                    // max is max(min(p0, p8), min(p4, p12)), on the raw pixels; v comes off once
+                    const short2_t br = __builtin_elementwise_min(__builtin_elementwise_max(p0, p8),
+                                                                  __builtin_elementwise_max(p4, p12));
+                    const short2_t dk = __builtin_elementwise_max(__builtin_elementwise_min(p0, p8),
+                                                                  __builtin_elementwise_min(p4, p12));
+                    // max(br - v, v - dk) - (tq + 1) >= 0 <=> the pixel passes; sign in bits 15 / 31
+                    q[h] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(br - v, v - dk) - tq1);
                 }
                 // sign bytes of the 4 pixels -> bit k (clear sign = pass)
                 const uint32_t sb = ~__builtin_amdgcn_perm(q[1], q[0], 0x07050301u) & 0x80808080u;
@@ -662,8 +667,8 @@ __global__ __launch_bounds__(256) void k_level_tiles(const uint8_t* __restrict__
     for (int i = tid; i < (kTH / 2) * (kTW / 4); i += 256) {
         const int rp = i >> 4, c = 4 * (i & 15);
         const int r = 2 * rp, y = Y0 + r, x = X0 + c;
-        if (y >= g.h || x >= g.w) continue;  // kTH is even: row y + 1 is then out too
-        const bool two = y + 1 < g.h;
+        if (y >= gh || x >= gw) continue;  // kTH is even: row y + 1 is then out too
+        const bool two = y + 1 < gh;
         uint4 q[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) q[k] = *(const uint4*)&s_rowp[rp + k][c];
@@ -690,21 +695,21 @@ __global__ __launch_bounds__(256) void k_level_tiles(const uint8_t* __restrict__
             po |= (vo > 255 ? 255u : vo) << (8 * k);
         }
         const uint32_t me = *(const uint32_t*)&s_m[r][c], mo = *(const uint32_t*)&s_m[r + 1][c];
-        const size_t off = (size_t)y * g.pitch + x;
-        if (x + 4 <= g.w) {
+        const size_t off = (size_t)y * gpitch + x;
+        if (x + 4 <= gw) {
             *(uint32_t*)(bout + off) = pe;
             *(uint32_t*)(mout + off) = me;
             if (two) {
-                *(uint32_t*)(bout + off + g.pitch) = po;
-                *(uint32_t*)(mout + off + g.pitch) = mo;
+                *(uint32_t*)(bout + off + gpitch) = po;
+                *(uint32_t*)(mout + off + gpitch) = mo;
             }
         } else {
-            for (int k = 0; x + k < g.w; k++) {
+            for (int k = 0; x + k < gw; k++) {
                 bout[off + k] = (uint8_t)(pe >> (8 * k));
                 mout[off + k] = (uint8_t)(me >> (8 * k));
                 if (two) {
-                    bout[off + g.pitch + k] = (uint8_t)(po >> (8 * k));
-                    mout[off + g.pitch + k] = (uint8_t)(mo >> (8 * k));
+                    bout[off + gpitch + k] = (uint8_t)(po >> (8 * k));
+                    mout[off + gpitch + k] = (uint8_t)(mo >> (8 * k));
                 }
             }
         }
