@@ -1062,6 +1062,82 @@ int orbx_optimize_sim3_batch_device(orbx_matcher* m, const orbx_optimize_sim3_ba
  * with B = 1, one synchronisation; the same bytes as the batch form gives that candidate. */
 int orbx_optimize_sim3(orbx_matcher* m, const orbx_optimize_sim3_batch* os);
 
+/* ---- LocalMapping::CreateNewMapPoints: triangulation and tests of the matched pairs ----
+ * The second half of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:307-501) for the
+ * vMatchedPairs that orbx_search_for_triangulation_batch_device left in HBM, with
+ * KeyFrame::UnprojectStereo (src/KeyFrame.cc:666-679) and MapPoint::UpdateNormalAndDepth for
+ * the two observations of a new point (src/MapPoint.cc:386-439).  One thread per matched pair.
+ * Float inputs are widened to double, everything after is double, outputs are rounded to float
+ * once; no floating-point value crosses lanes, so a pair's bytes are the same whatever the
+ * batch around it.  DESIGN.md §4.18.
+ *
+ * One KeyFrame as the triangulation reads it.  Device pointers (cap slots each), except Tcw. */
+typedef struct {
+    const orbx_keypoint* keys_un; /* mvKeysUn */
+    const orbx_keypoint* keys;    /* mvKeys (UnprojectStereo reads these) or NULL: keys_un */
+    const float* u_right;         /* mvuRight or NULL (monocular) */
+    const float* depth;           /* mvDepth or NULL: the float mbf / (keys[i].x - u_right[i]), as
+                                   * ComputeStereoMatches derived it (Frame.cc:852-856); gathered
+                                   * neighbours carry u_right but not mvDepth */
+    const int32_t* n;             /* N (one int; min(*n, cap) keypoints are read) */
+    float Tcw[12];                /* host: mTcw rows 0..2 */
+} orbx_keyframe_geom_device;
+
+/* Per pair slot [p][k], k < npairs[p] (slots past a row's count are neither read nor written).
+ * Every pointer may be NULL.
+ *   reason: 0 accepted, 1 no branch (low parallax and no stereo; also a stereo branch whose
+ *     mvDepth is not positive, where the reference dereferences an empty Mat), 2 w == 0 (cc:384),
+ *     3 z1 <= 0, 4 z2 <= 0, 5 reprojection in KF1 (cc:412-430), 6 reprojection in KF2 (cc:437-454;
+ *     its stereo form uses KF1's mbf, cc:446: the call has one mbf), 7 dist1 == 0 || dist2 == 0,
+ *     8 scale ratio (cc:475), 9 idx1 outside [0, N1) or idx2 outside [0, N2).
+ *   method: the branch taken, 1 linear (cc:369-387), 2 UnprojectStereo of KF1, 3 of KF2, 0 none
+ *     (reasons 1 and 9).  A rejected slot keeps the branch it was rejected after.
+ *   pos, normal, max_distance, min_distance: the new MapPoint's mWorldPos, mNormalVector,
+ *     mfMaxDistance, mfMinDistance (the orbx_mappoints_device columns); 0 in rejected slots.
+ *   nnew[p]: accepted slots of row p; new_idx[p][j], j < nnew[p]: their k in pair order, the
+ *     order the reference creates the MapPoints in (entries from nnew[p] on are not written).
+ * Octaves are clamped into [0, nlevels).  ratioFactor = 1.5 * scale_factors[1]. */
+typedef struct {
+    uint8_t* reason;       /* [P][cap] */
+    uint8_t* method;       /* [P][cap] */
+    float* pos;            /* [P][cap][3] */
+    float* normal;         /* [P][cap][3] */
+    float* max_distance;   /* [P][cap] */
+    float* min_distance;   /* [P][cap] */
+    int32_t* nnew;         /* [P] */
+    int32_t* new_idx;      /* [P][cap] */
+} orbx_new_mappoints;
+
+/* For p < npairs: KF1 = kfs[pairs[2p]], KF2 = kfs[pairs[2p+1]] (host table, the one the search
+ * call takes), matched pairs d_pairs[p][k] = (idx1, idx2), k < min(d_npairs[p], cap), exactly as
+ * orbx_search_for_triangulation_batch_device leaves them.  `cam` gives fx, fy, cx, cy and the
+ * level tables (nlevels, scale_factors, level_sigma2); mb and mbf are KF1's (the reference
+ * reads pKF2->mb for KF2's stereo parallax: one rig, one value).  Enqueued on `stream` (or the
+ * matcher's) without synchronising; the host tables are staged through pinned memory, so they
+ * may be reused on return.  cap <= 8192.
+ * Pairs are independent: in the reference a point created with neighbour i makes
+ * SearchForTriangulation skip that idx1 for neighbour i+1 (GetMapPoint(idx1) is set by then);
+ * the batched search does not see that, and neither does this call -- a caller that wants the
+ * reference's sequence drops, in neighbour order, the new points whose idx1 an earlier
+ * neighbour already filled.  ComputeDistinctiveDescriptors of the new points is
+ * orbx_compute_distinctive_descriptors_device over their two observations; adding them to the
+ * map (orbx_mappoints_device rows, AddObservation, AddMapPoint) stays with the caller.
+ * ORBX_ERR_ARG, decided before any device call: a null required pointer, cap <= 0 or > 8192, a
+ * negative count, bad level tables, a pair index outside [0, nkf). */
+int orbx_triangulate_pairs_batch_device(orbx_matcher* m, int nkf, const orbx_keyframe_geom_device* kfs,
+                                        const orbx_frame_view* cam, int npairs, const int32_t* pairs, int cap,
+                                        const int32_t* d_pairs, const int32_t* d_npairs, float mb, float mbf,
+                                        const orbx_new_mappoints* out, void* stream);
+
+/* The single-pair host form: every pointer of kf1, kf2 and out is a host pointer (kf->n points
+ * to one count, arrays of *n entries), matched: nmatched x (idx1, idx2), nmatched <= 8192; out's
+ * rows have nmatched slots (nnew: one int).  One upload, the batch kernel with one keyframe
+ * pair, one synchronisation; the same bytes as the batch form gives that pair.  Its wall time
+ * is orbx_matcher_last_call_us. */
+int orbx_triangulate_pairs(orbx_matcher* m, const orbx_keyframe_geom_device* kf1,
+                           const orbx_keyframe_geom_device* kf2, const orbx_frame_view* cam, int nmatched,
+                           const int32_t* matched, float mb, float mbf, const orbx_new_mappoints* out);
+
 /* Alternative kernel forms and diagnostics switches, process-wide (tests and A/B tools;
  * the product reads no environment).  Names: "pz_seg" (pyramid levels per launch, 0 = one
  * launch), "pz_byte" (byte-read k_pyramid), "desc_tiles" (tile-major describe),

@@ -332,6 +332,75 @@ public:
     }
 };
 
+// LocalMapping::CreateNewMapPoints' triangulation and tests (src/LocalMapping.cc:307-501) for one
+// keyframe pair on host arrays (orbx_triangulate_pairs).
+class LocalMapping {
+public:
+    // One KeyFrame as the triangulation reads it: mvKeysUn, mvKeys (empty: mvKeysUn), mvuRight
+    // (empty: monocular), mvDepth (empty: mbf / (mvKeys.x - mvuRight) in float), mTcw rows 0..2.
+    struct KeyFrameGeom {
+        std::vector<orbx_keypoint> mvKeysUn, mvKeys;
+        std::vector<float> mvuRight, mvDepth;
+        float mTcw[12];
+    };
+    // The new MapPoints of one pair row: per matched pair the reason (0 = accepted) and the branch
+    // taken, the point's mWorldPos / mNormalVector / mfMaxDistance / mfMinDistance, and the accepted
+    // slots in the order the reference creates the points in.
+    struct NewMapPoints {
+        std::vector<uint8_t> reason, method;
+        std::vector<float> pos, normal, maxDistance, minDistance;
+        std::vector<int32_t> newIdx;
+    };
+    // vMatchedIndices: (idx1, idx2) per matched pair, as SearchForTriangulation returns them.  cam:
+    // fx fy cx cy and the level tables; mb / mbf of KF1.  Returns nnew.
+    static int TriangulatePairs(ORBmatcher& matcher, const KeyFrameGeom& KF1, const KeyFrameGeom& KF2,
+                                const orbx_frame_view& cam, const std::vector<int32_t>& vMatchedIndices, float mb,
+                                float mbf, NewMapPoints& out) {
+        const int k = (int)(vMatchedIndices.size() / 2);
+        const int32_t n1 = (int32_t)KF1.mvKeysUn.size(), n2 = (int32_t)KF2.mvKeysUn.size();
+        auto sized = [](const KeyFrameGeom& K, size_t n) {
+            return (K.mvKeys.empty() || K.mvKeys.size() == n) && (K.mvuRight.empty() || K.mvuRight.size() == n) &&
+                   (K.mvDepth.empty() || K.mvDepth.size() == n);
+        };
+        if (!sized(KF1, (size_t)n1) || !sized(KF2, (size_t)n2))
+            throw std::runtime_error("TriangulatePairs: array sizes differ");
+        const orbx_keypoint kp0{};  // the call takes no null mvKeysUn: an empty one gets one spare element
+        auto rec = [&kp0](const KeyFrameGeom& K, const int32_t* n) {
+            orbx_keyframe_geom_device g{};
+            g.keys_un = K.mvKeysUn.empty() ? &kp0 : K.mvKeysUn.data();
+            g.keys = K.mvKeys.empty() ? nullptr : K.mvKeys.data();
+            g.u_right = K.mvuRight.empty() ? nullptr : K.mvuRight.data();
+            g.depth = K.mvDepth.empty() ? nullptr : K.mvDepth.data();
+            g.n = n;
+            for (int i = 0; i < 12; i++) g.Tcw[i] = K.mTcw[i];
+            return g;
+        };
+        const orbx_keyframe_geom_device g1 = rec(KF1, &n1), g2 = rec(KF2, &n2);
+        const size_t c = (size_t)(k > 0 ? k : 1);
+        out.reason.assign(c, 0);
+        out.method.assign(c, 0);
+        out.pos.assign(3 * c, 0.0f);
+        out.normal.assign(3 * c, 0.0f);
+        out.maxDistance.assign(c, 0.0f);
+        out.minDistance.assign(c, 0.0f);
+        out.newIdx.assign(c, 0);
+        int32_t nnew = 0;
+        const orbx_new_mappoints o{out.reason.data(), out.method.data(), out.pos.data(), out.normal.data(),
+                                   out.maxDistance.data(), out.minDistance.data(), &nnew, out.newIdx.data()};
+        const int32_t none[2] = {-1, -1};
+        check(orbx_triangulate_pairs(matcher.handle(), &g1, &g2, &cam, k, k > 0 ? vMatchedIndices.data() : none, mb, mbf,
+                                     &o));
+        out.reason.resize((size_t)k);
+        out.method.resize((size_t)k);
+        out.pos.resize(3 * (size_t)k);
+        out.normal.resize(3 * (size_t)k);
+        out.maxDistance.resize((size_t)k);
+        out.minDistance.resize((size_t)k);
+        out.newIdx.resize((size_t)nnew);
+        return nnew;
+    }
+};
+
 // DBoW2::BowVector (BowVector.h:59-62): word id -> value, ascending.
 typedef std::map<int32_t, double> BowVector;
 

@@ -58,6 +58,7 @@ EXPORTED = [
     "orbx_kfdb_detect_loop_candidates", "orbx_pose_optimization_batch_device", "orbx_pose_optimization",
     "orbx_sim3_create", "orbx_sim3_destroy", "orbx_sim3_set_batch_device", "orbx_sim3_iterate_device", "orbx_sim3_set",
     "orbx_sim3_iterate", "orbx_sim3_draws", "orbx_optimize_sim3_batch_device", "orbx_optimize_sim3",
+    "orbx_triangulate_pairs_batch_device", "orbx_triangulate_pairs",
 ]
 
 ORBX_DEPTH_U16 = 0
@@ -158,6 +159,22 @@ class OptimizeSim3Batch(C.Structure):
                 ("th2", C.c_float), ("fix_scale", C.c_int), ("R12_opt", C.c_void_p), ("t12_opt", C.c_void_p),
                 ("s12_opt", C.c_void_p), ("ninliers", C.c_void_p), ("ncorr", C.c_void_p), ("nbad", C.c_void_p),
                 ("trace", C.c_void_p)]
+
+
+class KeyFrameGeomDevice(C.Structure):
+    """orbx_keyframe_geom_device: device pointers (host ones in orbx_triangulate_pairs) + the host pose."""
+    _fields_ = [("keys_un", C.c_void_p), ("keys", C.c_void_p), ("u_right", C.c_void_p), ("depth", C.c_void_p),
+                ("n", C.c_void_p), ("Tcw", C.c_float * 12)]
+
+
+class NewMapPoints(C.Structure):
+    """orbx_new_mappoints: the outputs of the triangulation, every one nullable."""
+    _fields_ = [(k, C.c_void_p) for k in ("reason", "method", "pos", "normal", "max_distance", "min_distance",
+                                          "nnew", "new_idx")]
+
+
+ORBX_TRIANGULATE_REASONS = ("accepted", "no branch", "w == 0", "z1 <= 0", "z2 <= 0", "reprojection KF1",
+                            "reprojection KF2", "distance 0", "scale ratio", "bad index")
 
 
 # ---- handle lifetime (DESIGN.md §1 "Teardown") ------------------------------------
@@ -362,6 +379,10 @@ def lib() -> C.CDLL:
     L.orbx_sim3_draws.argtypes = [i32p, C.c_int, C.c_int]
     L.orbx_optimize_sim3_batch_device.argtypes = [vp, C.POINTER(OptimizeSim3Batch), vp]
     L.orbx_optimize_sim3.argtypes = [vp, C.POINTER(OptimizeSim3Batch)]
+    L.orbx_triangulate_pairs_batch_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, i32p, C.c_int, vp, vp, C.c_float,
+                                                      C.c_float, C.POINTER(NewMapPoints), vp]
+    L.orbx_triangulate_pairs.argtypes = [vp, C.POINTER(KeyFrameGeomDevice), C.POINTER(KeyFrameGeomDevice), vp, C.c_int,
+                                         i32p, C.c_float, C.c_float, C.POINTER(NewMapPoints)]
     L.orbx_version.restype = C.c_char_p
     L.orbx_device_count.argtypes = [ip]
     L.orbx_last_error.restype = C.c_char_p

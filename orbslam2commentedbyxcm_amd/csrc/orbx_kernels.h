@@ -183,6 +183,41 @@ struct OptSim3Args {
 size_t opt_sim3_workspace_bytes(int batch, int cap1);
 hipError_t launch_opt_sim3(OptSim3Args A, int batch, char* workspace, hipStream_t stream);
 
+// k_triangulate_pairs (orbx_triangulate.hip): LocalMapping::CreateNewMapPoints' triangulation
+// and tests (LocalMapping.cc:307-501) over the matched pairs of `npairs` keyframe pairs, one
+// workgroup each.
+struct TriGeomKF {
+    const orbx_keypoint* keys_un;  // mvKeysUn
+    const orbx_keypoint* keys;     // mvKeys or null (= keys_un)
+    const float* u_right;          // mvuRight or null (monocular)
+    const float* depth;            // mvDepth or null (mbf / (mvKeys.x - mvuRight) in float)
+    const int32_t* n;              // N (one device int)
+    float Tcw[12];
+    double Ow[3];                  // -Rcw^T tcw in double (the host builds it)
+};
+struct TriGeomArgs {
+    const TriGeomKF* kfs;
+    const int32_t* pair_kf;        // [P][2] keyframe records of KF1, KF2
+    const int32_t* pairs;          // [P][cap][2] vMatchedPairs
+    const int32_t* npairs;         // [P]
+    int cap;                       // pair slots per row
+    int kcap;                      // keypoint slots per keyframe (N is clamped into [0, kcap])
+    float fx, fy, cx, cy, mb, mbf;
+    int nlevels;
+    float scale_factor;            // mfScaleFactor
+    const float* scale;            // [nlevels] mvScaleFactors (device)
+    const float* sigma2;           // [nlevels] mvLevelSigma2 (device)
+    uint8_t* reason;               // every output: [P][cap]... or null
+    uint8_t* method;
+    float* pos;
+    float* normal;
+    float* max_distance;
+    float* min_distance;
+    int32_t* nnew;                 // [P]
+    int32_t* new_idx;              // [P][cap]
+};
+hipError_t launch_triangulate_pairs(const TriGeomArgs& A, int npairs, hipStream_t stream);
+
 hipError_t launch_window_match(const uint8_t* qdesc, int nq, const uint8_t* tdesc, const int32_t* tlevel,
                                const int32_t* cand_off, const int32_t* cand, int tie_last,
                                int32_t* best_idx, int32_t* best_dist, int32_t* best_level,

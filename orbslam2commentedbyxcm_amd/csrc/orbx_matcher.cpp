@@ -233,6 +233,11 @@ struct orbx_matcher {
     size_t pscr_cap = 0;
     char* pstage = nullptr;
     size_t pstage_cap = 0;
+    // tables of orbx_triangulate_pairs_batch_device, and the single call's keyframes and results (device-only)
+    char* gscr = nullptr;
+    size_t gscr_cap = 0;
+    char* gstage = nullptr;
+    size_t gstage_cap = 0;
     StageRing stage;
     // wall time of the newest drop-in host call (entry to return), as a C++ caller sees it
     double last_call_us = 0.0;
@@ -449,6 +454,8 @@ void orbx_matcher_destroy(orbx_matcher* m) {
     if (m->lscr) (void)hipFree(m->lscr);
     if (m->pscr) (void)hipFree(m->pscr);
     if (m->pstage) (void)hipFree(m->pstage);
+    if (m->gscr) (void)hipFree(m->gscr);
+    if (m->gstage) (void)hipFree(m->gstage);
     m->stage.release();
     if (m->hmp) (void)hipHostFree(m->hmp);
     for (auto& slot : m->ev)
@@ -2332,6 +2339,196 @@ int orbx_optimize_sim3(orbx_matcher* m, const orbx_optimize_sim3_batch* os) {
     if (os->nbad) *os->nbad = c[2];
     if (os->trace) std::memcpy(os->trace, c + 3, 16);
     if (n1 > 0) std::memcpy(os->matches12, h.data() + 80, 4 * (size_t)n1);
+    return ORBX_OK;
+}
+
+static const char* triangulate_check(int nkf, const orbx_keyframe_geom_device* kfs, const orbx_frame_view* cam,
+                                     int npairs, const int32_t* pairs, int cap, const int32_t* d_pairs,
+                                     const int32_t* d_npairs, const orbx_new_mappoints* out) {
+    if (nkf < 0 || npairs < 0) return "negative count";
+    if (!cam || !out) return "null argument";
+    if (cap <= 0) return "bad cap";
+    if (cap > 8192) return "cap above 8192";
+    if (cam->nlevels < 1 || cam->nlevels > ORBX_MAX_LEVELS || !cam->scale_factors || !cam->level_sigma2)
+        return "bad level tables";
+    if (npairs == 0) return nullptr;
+    if (!kfs || !pairs || !d_pairs || !d_npairs) return "null buffer";
+    for (int k = 0; k < nkf; k++)
+        if (!kfs[k].keys_un || !kfs[k].n) return "null keyframe array";
+    for (int p = 0; p < npairs; p++) {
+        const int a = pairs[2 * p], b = pairs[2 * p + 1];
+        if (a < 0 || a >= nkf || b < 0 || b >= nkf) return "keyframe index out of range";
+    }
+    return nullptr;
+}
+
+// the kernel's record of one keyframe: Ow = -Rcw^T tcw in double, products summed left to right
+static TriGeomKF geom_record(const orbx_keyframe_geom_device& K) {
+    TriGeomKF g{K.keys_un, K.keys, K.u_right, K.depth, K.n, {}, {}};
+    std::memcpy(g.Tcw, K.Tcw, sizeof(g.Tcw));
+    const float* T = K.Tcw;
+    for (int k = 0; k < 3; k++)
+        g.Ow[k] = -(((double)T[k] * (double)T[3] + (double)T[4 + k] * (double)T[7]) + (double)T[8 + k] * (double)T[11]);
+    return g;
+}
+
+static int triangulate_launch(orbx_matcher* m, int nkf, const orbx_keyframe_geom_device* kfs, const orbx_frame_view* cam,
+                              int npairs, const int32_t* pairs, int cap, int kcap, const int32_t* d_pairs,
+                              const int32_t* d_npairs, float mb, float mbf, const orbx_new_mappoints* out,
+                              hipStream_t s) {
+    const size_t P = (size_t)npairs;
+    const size_t tab = pad(sizeof(TriGeomKF) * (size_t)nkf) + pad(8 * P) + 2 * pad(sizeof(float) * ORBX_MAX_LEVELS);
+    if (m->gscr_cap < tab) {
+        HIP_TRY(hipStreamSynchronize(s));
+        if (m->gscr) HIP_TRY(hipFree(m->gscr));
+        m->gscr = nullptr;
+        m->gscr_cap = 0;
+        HIP_TRY(hipMalloc((void**)&m->gscr, tab));
+        m->gscr_cap = tab;
+    }
+    char* h = nullptr;
+    int slot = 0;
+    HIP_TRY(m->stage.get(tab, &h, &slot));
+    std::memset(h, 0, tab);
+    const size_t o_kf = 0, o_pk = o_kf + pad(sizeof(TriGeomKF) * (size_t)nkf), o_sc = o_pk + pad(8 * P),
+                 o_sg = o_sc + pad(sizeof(float) * ORBX_MAX_LEVELS);
+    auto* hk = (TriGeomKF*)(h + o_kf);
+    for (int k = 0; k < nkf; k++) hk[k] = geom_record(kfs[k]);
+    std::memcpy(h + o_pk, pairs, 8 * P);
+    for (int l = 0; l < cam->nlevels; l++) {
+        ((float*)(h + o_sc))[l] = cam->scale_factors[l];
+        ((float*)(h + o_sg))[l] = cam->level_sigma2[l];
+    }
+    HIP_TRY(hipMemcpyAsync(m->gscr, h, tab, hipMemcpyHostToDevice, s));
+    HIP_TRY(m->stage.copied(slot, s));
+    TriGeomArgs A{};
+    A.kfs = (const TriGeomKF*)(m->gscr + o_kf);
+    A.pair_kf = (const int32_t*)(m->gscr + o_pk);
+    A.pairs = d_pairs;
+    A.npairs = d_npairs;
+    A.cap = cap;
+    A.kcap = kcap;
+    A.fx = cam->fx;
+    A.fy = cam->fy;
+    A.cx = cam->cx;
+    A.cy = cam->cy;
+    A.mb = mb;
+    A.mbf = mbf;
+    A.nlevels = cam->nlevels;
+    A.scale_factor = cam->nlevels > 1 ? cam->scale_factors[1] : 1.0f;  // mfScaleFactor
+    A.scale = (const float*)(m->gscr + o_sc);
+    A.sigma2 = (const float*)(m->gscr + o_sg);
+    A.reason = out->reason;
+    A.method = out->method;
+    A.pos = out->pos;
+    A.normal = out->normal;
+    A.max_distance = out->max_distance;
+    A.min_distance = out->min_distance;
+    A.nnew = out->nnew;
+    A.new_idx = out->new_idx;
+    HIP_TRY(launch_triangulate_pairs(A, npairs, s));
+    return ORBX_OK;
+}
+
+// LocalMapping::CreateNewMapPoints' triangulation and tests (LocalMapping.cc:307-501) over the
+// matched pairs of many keyframe pairs in HBM (see include/orbx.h)
+int orbx_triangulate_pairs_batch_device(orbx_matcher* m, int nkf, const orbx_keyframe_geom_device* kfs,
+                                        const orbx_frame_view* cam, int npairs, const int32_t* pairs, int cap,
+                                        const int32_t* d_pairs, const int32_t* d_npairs, float mb, float mbf,
+                                        const orbx_new_mappoints* out, void* stream) {
+    // the arguments first, so that they are judged with or without a matcher (and a GPU)
+    if (const char* why = triangulate_check(nkf, kfs, cam, npairs, pairs, cap, d_pairs, d_npairs, out))
+        return fail(ORBX_ERR_ARG, why);
+    if (!m) return fail(ORBX_ERR_ARG, "null matcher");
+    if (npairs == 0) return ORBX_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    return triangulate_launch(m, nkf, kfs, cam, npairs, pairs, cap, cap, d_pairs, d_npairs, mb, mbf, out,
+                              stream ? (hipStream_t)stream : m->stream);
+}
+
+// The single-pair host form: two staged keyframes, the batch kernel, one synchronisation.
+int orbx_triangulate_pairs(orbx_matcher* m, const orbx_keyframe_geom_device* kf1,
+                           const orbx_keyframe_geom_device* kf2, const orbx_frame_view* cam, int nmatched,
+                           const int32_t* matched, float mb, float mbf, const orbx_new_mappoints* out) {
+    if (!kf1 || !kf2) return fail(ORBX_ERR_ARG, "null keyframe");
+    if (nmatched < 0) return fail(ORBX_ERR_ARG, "negative count");
+    if (nmatched > 8192) return fail(ORBX_ERR_ARG, "more than 8192 matched pairs");
+    const orbx_keyframe_geom_device two[2] = {*kf1, *kf2};
+    const int32_t pk[2] = {0, 1};
+    const int c = nmatched > 0 ? nmatched : 1;
+    if (nmatched > 0 && !matched) return fail(ORBX_ERR_ARG, "null buffer");
+    // the device arrays do not exist yet: pk stands in for them in the check
+    if (const char* why = triangulate_check(2, two, cam, 1, pk, c, pk, pk, out)) return fail(ORBX_ERR_ARG, why);
+    const int n[2] = {*kf1->n, *kf2->n};
+    if (n[0] < 0 || n[1] < 0) return fail(ORBX_ERR_ARG, "negative count");
+    if (!m) return fail(ORBX_ERR_ARG, "null matcher");
+    CallClock clock(m);
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    const int kcap = std::max(1, std::max(n[0], n[1]));
+    // per keyframe: keys_un, keys, u_right, depth (kcap slots each); then the matched pairs,
+    // {n1, n2, nmatched}; then the outputs as one block: nnew, new_idx, max, min, pos, normal,
+    // reason, method
+    const size_t kb = pad(sizeof(orbx_keypoint) * (size_t)kcap), fb = pad(4 * (size_t)kcap);
+    const size_t per_kf = 2 * kb + 2 * fb;
+    const size_t o_pairs = 2 * per_kf, o_cnt = o_pairs + pad(8 * (size_t)c), o_out = o_cnt + pad(16);
+    const size_t C = (size_t)c;
+    const size_t q_new = 0, q_idx = 16, q_max = q_idx + 4 * C, q_min = q_max + 4 * C, q_pos = q_min + 4 * C,
+                 q_nrm = q_pos + 12 * C, q_rsn = q_nrm + 12 * C, q_mth = q_rsn + C, out_bytes = q_mth + C;
+    const size_t total = o_out + pad(out_bytes);
+    if (m->gstage_cap < total) {
+        HIP_TRY(hipStreamSynchronize(s));
+        if (m->gstage) HIP_TRY(hipFree(m->gstage));
+        m->gstage = nullptr;
+        m->gstage_cap = 0;
+        HIP_TRY(hipMalloc((void**)&m->gstage, total));
+        m->gstage_cap = total;
+    }
+    char* p = m->gstage;
+    orbx_keyframe_geom_device d[2];
+    for (int k = 0; k < 2; k++) {
+        char* b = p + per_kf * k;
+        const orbx_keyframe_geom_device& K = two[k];
+        d[k] = K;
+        const size_t nk = (size_t)n[k];
+        d[k].keys_un = (const orbx_keypoint*)b;
+        d[k].keys = K.keys ? (const orbx_keypoint*)(b + kb) : nullptr;
+        d[k].u_right = K.u_right ? (const float*)(b + 2 * kb) : nullptr;
+        d[k].depth = K.depth ? (const float*)(b + 2 * kb + fb) : nullptr;
+        d[k].n = (const int32_t*)(p + o_cnt) + k;
+        if (nk) {
+            HIP_TRY(hipMemcpyAsync(b, K.keys_un, sizeof(orbx_keypoint) * nk, hipMemcpyHostToDevice, s));
+            if (K.keys) HIP_TRY(hipMemcpyAsync(b + kb, K.keys, sizeof(orbx_keypoint) * nk, hipMemcpyHostToDevice, s));
+            if (K.u_right) HIP_TRY(hipMemcpyAsync(b + 2 * kb, K.u_right, 4 * nk, hipMemcpyHostToDevice, s));
+            if (K.depth) HIP_TRY(hipMemcpyAsync(b + 2 * kb + fb, K.depth, 4 * nk, hipMemcpyHostToDevice, s));
+        }
+    }
+    if (nmatched > 0) HIP_TRY(hipMemcpyAsync(p + o_pairs, matched, 8 * (size_t)nmatched, hipMemcpyHostToDevice, s));
+    const int32_t cnt[4] = {n[0], n[1], nmatched, 0};
+    HIP_TRY(hipMemcpyAsync(p + o_cnt, cnt, sizeof(cnt), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(p + o_out, 0, out_bytes, s));
+    char* o = p + o_out;
+    const orbx_new_mappoints dout{(uint8_t*)(o + q_rsn), (uint8_t*)(o + q_mth), (float*)(o + q_pos), (float*)(o + q_nrm),
+                                  (float*)(o + q_max), (float*)(o + q_min), (int32_t*)(o + q_new), (int32_t*)(o + q_idx)};
+    const int rc = triangulate_launch(m, 2, d, cam, 1, pk, c, kcap, (const int32_t*)(p + o_pairs),
+                                      (const int32_t*)(p + o_cnt) + 2, mb, mbf, &dout, s);
+    if (rc) return rc;
+    std::vector<char> h(out_bytes);
+    HIP_TRY(hipMemcpyAsync(h.data(), o, out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const size_t nm = (size_t)nmatched;
+    int32_t nnew = 0;
+    std::memcpy(&nnew, h.data() + q_new, 4);
+    if (out->nnew) *out->nnew = nnew;
+    if (out->new_idx && nnew > 0) std::memcpy(out->new_idx, h.data() + q_idx, 4 * (size_t)nnew);
+    if (nm) {
+        if (out->max_distance) std::memcpy(out->max_distance, h.data() + q_max, 4 * nm);
+        if (out->min_distance) std::memcpy(out->min_distance, h.data() + q_min, 4 * nm);
+        if (out->pos) std::memcpy(out->pos, h.data() + q_pos, 12 * nm);
+        if (out->normal) std::memcpy(out->normal, h.data() + q_nrm, 12 * nm);
+        if (out->reason) std::memcpy(out->reason, h.data() + q_rsn, nm);
+        if (out->method) std::memcpy(out->method, h.data() + q_mth, nm);
+    }
     return ORBX_OK;
 }
 

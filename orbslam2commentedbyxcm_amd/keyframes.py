@@ -17,7 +17,13 @@ One step on every rank = for its B stereo keyframes of a W*B-keyframe window:
    local keyframe against its covisible neighbours, which live on the other ranks
    (keyframe g of the window is on rank g % W): the baseline test (cc:270-283), F12
    (ComputeF12, cc:606-625) and SearchForTriangulation (ORBmatcher.cc:850-1056) of every
-   pair in one launch (orbx_search_for_triangulation_batch_device), ORBmatcher(0.6, false).
+   pair in one launch (orbx_search_for_triangulation_batch_device), ORBmatcher(0.6, false);
+6. with ``triangulate=True``, the rest of that function (LocalMapping.cc:307-501) on the same
+   stream and the same vMatchedPairs: linear triangulation or stereo back-projection, the
+   depth-sign / reprojection / scale tests and the new MapPoints' position, normal and distance
+   range (orbx_triangulate_pairs_batch_device; mapping.Triangulator).  Neighbours are read
+   from the gathered buffer, which carries mvuRight but no mvDepth (derived); the local KF1
+   of each pair uses this rank's mvDepth.  Off by default: then nothing above changes.
 
 Step k+1's extraction overlaps step k's stereo / BoW / gather / triangulation: sets of
 extractor pairs, slabs, gathered buffers and triangulation outputs rotate (four by
@@ -206,7 +212,7 @@ class StereoKeyFramePipeline:
     def __init__(self, batch: int, rank: int = 0, world: int = 1, device: int = 0, nn: int = 10, seq_seed: int = 3,
                  vocab_text: bytes | None = None, settings: dict | None = None, group=None, windows: int = 1,
                  on_step_done=None, collective: bool = False, level0_in_place: bool = True, nsets: int = 4,
-                 lane_offset_stage: int = 3, gather_async: bool = True):
+                 lane_offset_stage: int = 3, gather_async: bool = True, triangulate: bool = False):
         import torch
 
         from . import synth
@@ -338,13 +344,40 @@ class StereoKeyFramePipeline:
         from .matcher import keyframe_table
         bufs = self.gathered if self.collective else self.slabs
         self._tabs = [keyframe_table(self.lay.records(b.data_ptr(), self.world, self._rec_poses)) for b in bufs]
+        # triangulate: the second half of CreateNewMapPoints (LocalMapping.cc:307-501) on the
+        # triangulation stream, right after the search and on its d_pairs / d_npairs.  Records
+        # [0, W*B): the keyframes of the gathered buffer (mvuRight, no mvDepth: derived), then one
+        # record per local keyframe with this rank's mvDepth; KF1 of a pair is always local
+        self.triangulate = bool(triangulate)
+        if self.triangulate:
+            from .mapping import Triangulator, keyframe_geom_device, keyframe_geom_table, new_mappoints_table
+            self.tg = Triangulator(self.tri)
+            self.new_points = [new_mappoints_table(P, self.cap, self.dev) for _ in range(self.nsets)]
+            nrec = self.world * self.B
+            self._gtabs = []
+            for k, b in enumerate(bufs):
+                recs = []
+                for q in range(self.world):
+                    for i in range(self.B):
+                        a = {name: self.lay.address(b.data_ptr(), q, i, name) for name in ("kps", "n", "u_right")}
+                        recs.append(keyframe_geom_device(a["kps"], a["n"], win_poses[q * self.B + i], a["u_right"]))
+                for i in range(self.B):
+                    v = self.sv[k]
+                    recs.append(keyframe_geom_device(v["kps"][i], v["n"][i:i + 1], self.poses[self.local[i]],
+                                                     v["u_right"][i], self.right[k]["depth"][i]))
+                self._gtabs.append(keyframe_geom_table(recs))
+            gp = np.array(self.plan.pairs, np.int32).reshape(-1, 2).copy()
+            for p in range(len(gp)):
+                gp[p, 0] = nrec + int(gp[p, 0]) - self.rank * self.B
+            self._geom_pairs = gp
 
     def close(self):
         """Wait for this pipeline's work, then release its matchers, vocabulary, extractor
         pairs and the streams it created (idempotent)."""
         from .extractor import release_owned
         release_owned(self, streams=[getattr(self, "ts", None), getattr(self, "ms", None)],
-                      owners=[getattr(self, "stereo", None), getattr(self, "tri", None), getattr(self, "voc", None),
+                      owners=[getattr(self, "tg", None), getattr(self, "stereo", None), getattr(self, "tri", None),
+                              getattr(self, "voc", None),
                               *(e for pair in getattr(self, "sets", []) for e in pair)],
                       own_streams=["_own_ts", "_own_ms"])
 
@@ -407,6 +440,9 @@ class StereoKeyFramePipeline:
             self.tri.SearchForTriangulationBatchDevice(self._tabs[k], self.cam, self.plan.pairs, self.plan.F12,
                                                        self.cap, self.m12[k], self.tri_pairs[k], self.tri_n[k],
                                                        stream=ts)
+            if self.triangulate:
+                self.tg.triangulate_pairs_batch_device(self._gtabs[k], self.cam, self._geom_pairs, self.cap,
+                                                       self.tri_pairs[k], self.tri_n[k], self.new_points[k], stream=ts)
         if self.on_step_done is not None:
             self.on_step_done(k)
         self.ev_m[k].record(ts)  # after the stereo, BoW and gather (waited for) and the triangulation
@@ -452,6 +488,8 @@ class StereoKeyFramePipeline:
              "tri_pairs": self.tri_pairs[k][:P]}
         if self.collective:
             r["gathered"] = self.gathered[k]
+        if self.triangulate:  # orbx_new_mappoints of the step's pairs: new_reason, new_pos, ... (P rows)
+            r.update({"new_" + name: t[:P] for name, t in self.new_points[k].items()})
         return r
 
     def to_host(self, r: dict) -> dict:
