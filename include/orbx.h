@@ -1138,6 +1138,127 @@ int orbx_triangulate_pairs(orbx_matcher* m, const orbx_keyframe_geom_device* kf1
                            const orbx_keyframe_geom_device* kf2, const orbx_frame_view* cam, int nmatched,
                            const int32_t* matched, float mb, float mbf, const orbx_new_mappoints* out);
 
+/* ---- Initializer: H / F RANSAC and two-view reconstruction of monocular initialisation ----
+ * Initializer::Initialize(CurrentFrame, vMatches12, R21, t21, vP3D, vbTriangulated)
+ * (src/Initializer.cc:64-165) with everything under it -- Normalize (cc:1138-1200),
+ * FindHomography / FindFundamental (cc:179-309), ComputeH21 / ComputeF21 (cc:318-440),
+ * CheckHomography (cc:450-590), CheckFundamental (cc:597-735), ReconstructF (cc:749-890),
+ * ReconstructH (cc:905-1097), Triangulate, CheckRT (cc:1215-1379), DecomposeE -- for B
+ * independent frame pairs in HBM: the consumer of orbx_search_for_initialization's matches12.
+ * Float inputs are widened to double, everything after is double (thresholds 5.991, 3.841,
+ * 0.99998, 1.00001, 0.40 included), outputs are rounded to float once.  Floating-point sums
+ * over keypoints or correspondences have a fixed shape that depends only on n1 / n2 / N: a
+ * frame pair's bytes do not depend on the batch around it.  The host reads nothing back
+ * during a call.  DESIGN.md §4.19.
+ *   Correspondences: the slots i < n1 with 0 <= matches12[i] < n2, in slot order (mvMatches12,
+ *   cc:77-85); any other value skips the slot; N is their count.  Normalize runs over all n1
+ *   (n2) keypoints; a zero deviation gives inf / NaN as IEEE gives it, such hypotheses score 0
+ *   through failed comparisons and never become best.
+ *   sets [B][max_iterations][8] are indices into the N correspondences (mvSets;
+ *   orbx_initializer_sets gives the reference's).  A set with an index outside [0, N) or a
+ *   repeated index scores 0 for both models and sets ORBX_INIT_STATUS_BAD_SET.  N < 8: no
+ *   iteration, ok = 0, ORBX_INIT_STATUS_TOO_FEW (the reference is undefined there).
+ *   Best hypothesis: currentScore > score, strictly, from score = 0 (cc:235, 303): a tie keeps
+ *   the EARLIER iteration -- the opposite of Sim3Solver's `>=` (orbx_sim3_iterate_device).  If
+ *   no iteration scores above 0 the model matrix is the empty Mat (all 0) without inliers.
+ *   RH = SH / (SH + SF) > 0.40 reconstructs from H, otherwise (NaN included) from F, both with
+ *   minParallax 1.0 and minTriangulated 50.  The SVDs are one-sided Jacobi iterations in
+ *   double; their sign and order freedom only permutes the 4 / 8 motion hypotheses, and both
+ *   selection rules are blind to that.
+ * K is a host array; every other pointer is a device pointer (all are host pointers, and
+ * batch is 1, for orbx_initializer_initialize).
+ *
+ * orbx_initializer_create (the workspace for up to max_batch pairs of up to kcap <= 8192
+ * keypoints and max_iterations <= ORBX_INIT_MAX_ITERATIONS) borrows the matcher's device and
+ * stream; the matcher must outlive it.  orbx_initializer_destroy waits for that stream; after
+ * the library's unload destructor it releases nothing. */
+#define ORBX_INIT_MAX_ITERATIONS 4096
+#define ORBX_INIT_STATUS_BAD_SET 1 /* status bit 0: a set had an index outside [0, N) or a repeated one */
+#define ORBX_INIT_STATUS_TOO_FEW 2 /* status bit 1: N < 8 */
+typedef struct orbx_initializer orbx_initializer;
+int orbx_initializer_create(orbx_matcher* m, int max_batch, int kcap, int max_iterations, orbx_initializer** out);
+void orbx_initializer_destroy(orbx_initializer* s);
+
+typedef struct {
+    int batch;
+    int kcap;                    /* keypoint slots per row, <= the solver's kcap */
+    const int32_t* n1;           /* [B] keypoints of the reference frame, clamped into [0, kcap] */
+    const int32_t* n2;           /* [B] keypoints of the current frame */
+    const orbx_keypoint* keys1;  /* [B][kcap] mvKeysUn of the reference frame; x and y are read */
+    const orbx_keypoint* keys2;  /* [B][kcap] mvKeysUn of the current frame */
+    const int32_t* matches12;    /* [B][kcap] vMatches12 as orbx_search_for_initialization leaves it */
+    const float* K;              /* host: fx fy cx cy */
+    float sigma;                 /* mSigma, 1.0 in Tracking */
+    int max_iterations;          /* mMaxIterations, 200 in Tracking; <= the solver's */
+    const int32_t* sets;         /* [B][max_iterations][8] */
+} orbx_initializer_batch;
+
+/* Every output is a nullable device array (host pointers to one pair's for
+ * orbx_initializer_initialize).
+ *   ok: Initialize's return value.  model: 0 = ReconstructH ran, 1 = ReconstructF.
+ *   n_matches = N.  SH, SF, RH: the scores and their ratio.  best_it_H / best_it_F: the
+ *   iteration that holds the best score, -1 if none.  H21 / F21: its matrix (scale and sign
+ *   are as free as in the reference), all 0 if none.
+ *   inliers_H / inliers_F: vbMatchesInliersH / F indexed by the frame-1 keypoint, 0 at
+ *   unmatched slots below n1; n_inliers_H / F their counts.
+ *   R21, t21: all 0 (the empty Mat) when ok is 0.  p3d, triangulated: vP3D and vbTriangulated
+ *   of the winning hypothesis as CheckRT leaves them (zero point, flag 0 where it wrote
+ *   nothing); all 0 below n1 when ok is 0.
+ *   best_good, second_good: ReconstructH's bestGood and secondBestGood; for ReconstructF
+ *   maxGood and the largest of the other three counts.  n_similar: ReconstructF's, 0 for H.
+ *   parallax: the chosen hypothesis's (ReconstructH: bestParallax, -1 if no hypothesis has a
+ *   good point; 0 where d1/d2 or d2/d3 fails, with both counts 0).
+ *   status: the ORBX_INIT_STATUS_* bits.
+ * Entries of the [B][kcap] arrays at and beyond n1 are left untouched. */
+typedef struct {
+    int32_t* ok;            /* [B] */
+    int32_t* model;         /* [B] */
+    int32_t* n_matches;     /* [B] */
+    float* SH;              /* [B] */
+    float* SF;              /* [B] */
+    float* RH;              /* [B] */
+    int32_t* best_it_H;     /* [B] */
+    int32_t* best_it_F;     /* [B] */
+    float* H21;             /* [B][9] */
+    float* F21;             /* [B][9] */
+    uint8_t* inliers_H;     /* [B][kcap] */
+    uint8_t* inliers_F;     /* [B][kcap] */
+    int32_t* n_inliers_H;   /* [B] */
+    int32_t* n_inliers_F;   /* [B] */
+    float* R21;             /* [B][9] */
+    float* t21;             /* [B][3] */
+    float* p3d;             /* [B][kcap][3] */
+    uint8_t* triangulated;  /* [B][kcap] */
+    int32_t* best_good;     /* [B] */
+    int32_t* second_good;   /* [B] */
+    int32_t* n_similar;     /* [B] */
+    float* parallax;        /* [B] */
+    int32_t* status;        /* [B] */
+} orbx_initializer_result;
+
+/* Asynchronous on `stream` (or the matcher's); the calls on one solver share its workspace,
+ * so the caller keeps them in order.  ORBX_ERR_ARG, decided before any device call: a null
+ * argument or required pointer, batch outside [0, max_batch], kcap outside [1, the solver's],
+ * max_iterations outside [1, the solver's], sigma not positive. */
+int orbx_initializer_initialize_device(orbx_initializer* s, const orbx_initializer_batch* in,
+                                       const orbx_initializer_result* out, void* stream);
+
+/* The single-pair host form: every pointer of the structs is a host pointer and batch is 1
+ * (keys1 / matches12 hold *n1 entries, keys2 *n2, sets [max_iterations][8]; the per-keypoint
+ * outputs hold *n1 entries).  One upload, the batch kernels with B = 1, one synchronisation;
+ * the same bytes as the batch form gives that pair.  Its wall time is
+ * orbx_matcher_last_call_us. */
+int orbx_initializer_initialize(orbx_initializer* s, const orbx_initializer_batch* in,
+                                const orbx_initializer_result* out);
+
+/* The reference's mvSets for n correspondences (cc:103-123): sets [iterations][8], per
+ * iteration 8 draws RandomInt(0, size - 1) = int(((double)rand() / ((double)RAND_MAX + 1.0))
+ * * size) (DUtils/Random.cpp:47-49) without replacement, each removed by a swap with the back
+ * and a pop.  n < 8 gives zeros.  One deviation: srand(0) is called on every call, where the
+ * reference's SeedRandOnce(0) seeds once per process -- the first Initialize of a process is
+ * reproduced, later ones restart the sequence.  Host only, no GPU. */
+int orbx_initializer_sets(int32_t* sets, int n, int iterations);
+
 /* Alternative kernel forms and diagnostics switches, process-wide (tests and A/B tools;
  * the product reads no environment).  Names: "pz_seg" (pyramid levels per launch, 0 = one
  * launch), "pz_byte" (byte-read k_pyramid), "desc_tiles" (tile-major describe),

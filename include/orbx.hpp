@@ -654,4 +654,119 @@ private:
     float R_[9] = {}, t_[3] = {}, s_ = 0.0f;
 };
 
+// Initializer (include/Initializer.h, src/Initializer.cc:64-1415) on the arrays the adapter
+// extracts: mvKeysUn of the reference frame at construction (Initializer(ReferenceFrame, sigma,
+// iterations), cc:43-56, with K as fx fy cx cy), mvKeysUn of the current frame and vMatches12 per
+// call.  sets: 8 per iteration (empty: the reference's, from srand(0) and rand()).  Runs on the
+// matcher's handle and stream; the matcher must outlive it.
+class Initializer {
+public:
+    Initializer(ORBmatcher& matcher, const std::vector<orbx_keypoint>& mvKeys1, const float* K, float sigma = 1.0f,
+                int iterations = 200)
+        : m_(matcher.handle()), keys1_(mvKeys1), sigma_(sigma), its_(iterations) {
+        for (int i = 0; i < 4; i++) K_[i] = K[i];
+    }
+    ~Initializer() { orbx_initializer_destroy(h_); }
+    Initializer(const Initializer&) = delete;
+    Initializer& operator=(const Initializer&) = delete;
+
+    // Initialize(CurrentFrame, vMatches12, R21, t21, vP3D, vbTriangulated) (cc:64-165): R21 (9
+    // floats, row-major) and t21 (3) are empty when it returns false; vP3D holds 3 floats per
+    // keypoint of the reference frame.
+    bool Initialize(const std::vector<orbx_keypoint>& mvKeys2, const std::vector<int32_t>& vMatches12,
+                    std::vector<float>& R21, std::vector<float>& t21, std::vector<float>& vP3D,
+                    std::vector<bool>& vbTriangulated, const std::vector<int32_t>& sets = {}) {
+        const int32_t n1 = (int32_t)keys1_.size(), n2 = (int32_t)mvKeys2.size();
+        if (vMatches12.size() != keys1_.size())
+            throw Error(ORBX_ERR_ARG, "Initializer: one vMatches12 entry per keypoint of the reference frame");
+        const int kcap = std::max(1, std::max(n1, n2));
+        if (!h_ || kcap > kcap_) {
+            orbx_initializer_destroy(h_);
+            h_ = nullptr;
+            check(orbx_initializer_create(m_, 1, kcap, its_, &h_));
+            kcap_ = kcap;
+        }
+        std::vector<int32_t> s(sets);
+        if (s.empty()) {
+            int N = 0;
+            for (int32_t v : vMatches12) N += v >= 0 && v < n2;
+            s.resize((size_t)its_ * 8);
+            check(orbx_initializer_sets(s.data(), N, its_));
+        }
+        if (s.size() < (size_t)its_ * 8) throw Error(ORBX_ERR_ARG, "Initializer: fewer sets than iterations");
+        const orbx_keypoint none{};  // an empty frame: the array is not read
+        orbx_initializer_batch in{};
+        in.batch = 1;
+        in.kcap = kcap;
+        in.n1 = &n1;
+        in.n2 = &n2;
+        in.keys1 = n1 ? keys1_.data() : &none;
+        in.keys2 = n2 ? mvKeys2.data() : &none;
+        const int32_t no_match = -1;
+        in.matches12 = n1 ? vMatches12.data() : &no_match;
+        in.K = K_;
+        in.sigma = sigma_;
+        in.max_iterations = its_;
+        in.sets = s.data();
+        std::vector<uint8_t> tri((size_t)kcap, 0);
+        inliersH.assign((size_t)kcap, 0);
+        inliersF.assign((size_t)kcap, 0);
+        R21.assign(9, 0.0f);
+        t21.assign(3, 0.0f);
+        vP3D.assign((size_t)kcap * 3, 0.0f);
+        int32_t ok = 0;
+        orbx_initializer_result out{};
+        out.ok = &ok;
+        out.model = &model;
+        out.n_matches = &N;
+        out.SH = &SH;
+        out.SF = &SF;
+        out.RH = &RH;
+        out.best_it_H = &bestIterationH;
+        out.best_it_F = &bestIterationF;
+        out.H21 = H21;
+        out.F21 = F21;
+        out.inliers_H = inliersH.data();
+        out.inliers_F = inliersF.data();
+        out.n_inliers_H = &nInliersH;
+        out.n_inliers_F = &nInliersF;
+        out.R21 = R21.data();
+        out.t21 = t21.data();
+        out.p3d = vP3D.data();
+        out.triangulated = tri.data();
+        out.best_good = &bestGood;
+        out.second_good = &secondGood;
+        out.n_similar = &nSimilar;
+        out.parallax = &parallax;
+        out.status = &status;
+        check(orbx_initializer_initialize(h_, &in, &out));
+        vP3D.resize((size_t)n1 * 3);
+        inliersH.resize((size_t)n1);
+        inliersF.resize((size_t)n1);
+        vbTriangulated.assign((size_t)n1, false);
+        for (int i = 0; i < n1; i++) vbTriangulated[(size_t)i] = tri[(size_t)i] != 0;
+        if (!ok) {
+            R21.clear();
+            t21.clear();
+        }
+        return ok != 0;
+    }
+    orbx_initializer* handle() { return h_; }
+
+    // after an Initialize: the model that was reconstructed (0 = H, 1 = F), N, the scores, the
+    // best iterations (-1: none) and matrices, the inlier flags per keypoint of the reference
+    // frame, ReconstructH / F's counts, the chosen hypothesis's parallax, the ORBX_INIT_STATUS_* bits
+    int32_t model = 1, N = 0, bestIterationH = -1, bestIterationF = -1, nInliersH = 0, nInliersF = 0, bestGood = 0,
+            secondGood = 0, nSimilar = 0, status = 0;
+    float SH = 0.0f, SF = 0.0f, RH = 0.0f, parallax = 0.0f, H21[9] = {}, F21[9] = {};
+    std::vector<uint8_t> inliersH, inliersF;
+
+private:
+    orbx_matcher* m_;
+    orbx_initializer* h_ = nullptr;
+    std::vector<orbx_keypoint> keys1_;
+    float K_[4], sigma_;
+    int its_, kcap_ = 0;
+};
+
 }  // namespace orbx

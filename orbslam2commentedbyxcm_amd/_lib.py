@@ -59,6 +59,8 @@ EXPORTED = [
     "orbx_sim3_create", "orbx_sim3_destroy", "orbx_sim3_set_batch_device", "orbx_sim3_iterate_device", "orbx_sim3_set",
     "orbx_sim3_iterate", "orbx_sim3_draws", "orbx_optimize_sim3_batch_device", "orbx_optimize_sim3",
     "orbx_triangulate_pairs_batch_device", "orbx_triangulate_pairs",
+    "orbx_initializer_create", "orbx_initializer_destroy", "orbx_initializer_initialize_device",
+    "orbx_initializer_initialize", "orbx_initializer_sets",
 ]
 
 ORBX_DEPTH_U16 = 0
@@ -175,6 +177,28 @@ class NewMapPoints(C.Structure):
 
 ORBX_TRIANGULATE_REASONS = ("accepted", "no branch", "w == 0", "z1 <= 0", "z2 <= 0", "reprojection KF1",
                             "reprojection KF2", "distance 0", "scale ratio", "bad index")
+
+
+class InitializerBatch(C.Structure):
+    """orbx_initializer_batch."""
+    _fields_ = [("batch", C.c_int), ("kcap", C.c_int), ("n1", C.c_void_p), ("n2", C.c_void_p), ("keys1", C.c_void_p),
+                ("keys2", C.c_void_p), ("matches12", C.c_void_p), ("K", C.POINTER(C.c_float)), ("sigma", C.c_float),
+                ("max_iterations", C.c_int), ("sets", C.c_void_p)]
+
+
+INITIALIZER_RESULT_FIELDS = ("ok", "model", "n_matches", "SH", "SF", "RH", "best_it_H", "best_it_F", "H21", "F21",
+                             "inliers_H", "inliers_F", "n_inliers_H", "n_inliers_F", "R21", "t21", "p3d",
+                             "triangulated", "best_good", "second_good", "n_similar", "parallax", "status")
+
+
+class InitializerResult(C.Structure):
+    """orbx_initializer_result: every output nullable."""
+    _fields_ = [(k, C.c_void_p) for k in INITIALIZER_RESULT_FIELDS]
+
+
+ORBX_INIT_MAX_ITERATIONS = 4096
+ORBX_INIT_STATUS_BAD_SET = 1
+ORBX_INIT_STATUS_TOO_FEW = 2
 
 
 # ---- handle lifetime (DESIGN.md §1 "Teardown") ------------------------------------
@@ -383,6 +407,12 @@ def lib() -> C.CDLL:
                                                       C.c_float, C.POINTER(NewMapPoints), vp]
     L.orbx_triangulate_pairs.argtypes = [vp, C.POINTER(KeyFrameGeomDevice), C.POINTER(KeyFrameGeomDevice), vp, C.c_int,
                                          i32p, C.c_float, C.c_float, C.POINTER(NewMapPoints)]
+    L.orbx_initializer_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.orbx_initializer_destroy.argtypes = [vp]
+    L.orbx_initializer_destroy.restype = None
+    L.orbx_initializer_initialize_device.argtypes = [vp, C.POINTER(InitializerBatch), C.POINTER(InitializerResult), vp]
+    L.orbx_initializer_initialize.argtypes = [vp, C.POINTER(InitializerBatch), C.POINTER(InitializerResult)]
+    L.orbx_initializer_sets.argtypes = [i32p, C.c_int, C.c_int]
     L.orbx_version.restype = C.c_char_p
     L.orbx_device_count.argtypes = [ip]
     L.orbx_last_error.restype = C.c_char_p
