@@ -94,10 +94,6 @@ __device__ __forceinline__ void xcd_frame_block(int per_frame, int nframes, int&
 
 typedef unsigned short ushort2_t __attribute__((ext_vector_type(2)));
 
-#ifndef ORBX_PZ_QWORD
-#define ORBX_PZ_QWORD 0  // 1: k_pyramid<true> reads a source row window as two qword LDS reads (r05b: slower)
-#endif
-
 // 24 x 24 -> high 32 bits of the 48-bit product (v_mul_hi_u32_u24)
 __device__ __forceinline__ uint32_t mulhi24(uint32_t a, uint32_t b) {
     return (uint32_t)(((unsigned long long)(a & 0xffffff) * (b & 0xffffff)) >> 32);
@@ -125,18 +121,46 @@ __device__ __forceinline__ void store_owned_quad(uint8_t* o, int x, int ox0, int
     }
 }
 
+// The plan's (tile, level) rectangles and constants (orbx_geometry.h), each read as one
+// aligned 16-byte piece (scalar loads: they are the workgroup's) and unpacked from their
+// int16 halves.
+struct PzRec {
+    int x0, y0, x1, y1, ox0, oy0, ox1, oy1;  // needed and owned rectangles
+    int nq, G, rc;                           // width in quads, row groups, rows per group
+    int sstride, sxa, sy0;                   // the source level's LDS row stride and origin
+    uint32_t mul;                            // tid / min(nq, 256) = (tid * mul) >> 16
+};
+__device__ __forceinline__ PzRec pz_rec(const int16_t* rect, const int16_t* cons) {
+    const uint4 a = *(const uint4*)rect, b = *(const uint4*)cons;
+    auto lo = [](uint32_t v) { return (int)(int16_t)(v & 0xffffu); };
+    auto hi = [](uint32_t v) { return (int)v >> 16; };
+    PzRec r;
+    r.x0 = lo(a.x), r.y0 = hi(a.x), r.x1 = lo(a.y), r.y1 = hi(a.y);
+    r.ox0 = lo(a.z), r.oy0 = hi(a.z), r.ox1 = lo(a.w), r.oy1 = hi(a.w);
+    r.nq = lo(b.x), r.G = hi(b.x), r.rc = lo(b.y), r.sstride = hi(b.y);
+    r.sxa = lo(b.z), r.sy0 = hi(b.z), r.mul = b.w;
+    return r;
+}
+
 // Thread -> (column quad, row group) split of a level rectangle nq quads wide: G groups
-// of nqp lanes; the quotient comes from a float reciprocal (exact for tid < 256).
+// of nqp = min(nq, 256) lanes.  nq, G and the multiplier that divides tid by nqp come from
+// the plan's record: no division here.
 struct QuadSplit {
     int nqp, G, q, gr;
 };
-__device__ __forceinline__ QuadSplit quad_split(int nq, int tid) {
+__device__ __forceinline__ QuadSplit quad_split(const PzRec& rec, int tid) {
     QuadSplit s;
-    s.nqp = min(nq, 256);
-    s.G = 256 / s.nqp;
-    s.gr = (int)(((float)tid + 0.5f) * (1.0f / (float)s.nqp));
+    s.nqp = min(rec.nq, 256);
+    s.G = rec.G;
+    s.gr = (int)(((uint32_t)tid * rec.mul) >> 16);
     s.q = tid - s.gr * s.nqp;
     return s;
+}
+
+// A load at a 32-bit byte offset from a wave-uniform base (scalar base + vector offset)
+template <typename T>
+__device__ __forceinline__ T ld_off(const void* base, uint32_t byte_off) {
+    return *(const T*)((const uint8_t*)base + byte_off);
 }
 
 #ifdef ORBX_PZ_WAVES
@@ -148,7 +172,7 @@ template <bool WIN>
 __global__ __launch_bounds__(256) ORBX_PZ_ATTR void k_pyramid(const uint8_t* __restrict__ src, size_t frame_pitch, size_t stride,
                                                  int vec4, uint8_t* __restrict__ pyr, long long fb,
                                                  const LevelGeom* __restrict__ lv, int L,
-                                                 const int16_t* __restrict__ rtab, int pz_off, int tiles_pf,
+                                                 const int16_t* __restrict__ rtab, int pz_off, int pz_coff, int tiles_pf,
                                                  int nframes, int lds_a, int* __restrict__ status, int l0_store) {
     extern __shared__ __align__(16) uint8_t s_pz[];
     int f, tile;
@@ -157,18 +181,20 @@ __global__ __launch_bounds__(256) ORBX_PZ_ATTR void k_pyramid(const uint8_t* __r
     // the frame's status word starts clean here (k_octree ORs into it later on this stream):
     // no separate memset launch ahead of every extraction
     if (tile == 0 && tid == 0) status[f] = 0;
-    const int16_t* R = rtab + pz_off + (size_t)tile * L * 8;
+    const int16_t* R = rtab + pz_off + (size_t)tile * L * 8;  // 16-byte aligned records
+    const int16_t* Cn = rtab + pz_coff + (size_t)tile * L * kPzRec;
     uint8_t* const frame = pyr + (size_t)f * fb;
     // LDS rows of a level hold its needed columns widened to whole quads, [x0 & ~3, ...)
     // ---- level 0: load the needed rectangle into buffer A, write the owned part
     {
-        const int x0 = R[0], y0 = R[1], x1 = R[2], y1 = R[3];
-        const int ox0 = R[4], oy0 = R[5], ox1 = R[6], oy1 = R[7];
+        const PzRec rec = pz_rec(R, Cn);
+        const int x0 = rec.x0, y0 = rec.y0, x1 = rec.x1, y1 = rec.y1;
+        const int ox0 = rec.ox0, oy0 = rec.oy0, ox1 = rec.ox1, oy1 = rec.oy1;
         const LevelGeom& g = lv[0];
         if (x1 > x0 && y1 > y0) {
             const int xa = x0 & ~3;
-            const int nq = (x1 - xa + 3) >> 2, hn = y1 - y0, ostride = 4 * nq;
-            const QuadSplit sp = quad_split(nq, tid);
+            const int nq = rec.nq, hn = y1 - y0, ostride = 4 * nq;
+            const QuadSplit sp = quad_split(rec, tid);
             const uint8_t* in = src + (size_t)f * frame_pitch;
             if (sp.gr < sp.G) {
                 for (int qq = sp.q; qq < nq; qq += sp.nqp) {
@@ -222,154 +248,163 @@ __global__ __launch_bounds__(256) ORBX_PZ_ATTR void k_pyramid(const uint8_t* __r
     // h = S[sx0]*a0 + S[sx1]*a1 is kept as hm = h & ~15 and the vertical step
     // (b*(h>>4))>>16 = (b*hm)>>20 is one v_mul_hi_u32_u24 of (b << 12, hm).  The result
     // needs no saturation: a0 + a1 <= 2049 and b0 + b1 <= 2049 bound it by 255.
+    // Everything that depends only on (tile, level) -- the split, the rows per thread, the
+    // source rectangle's origin and stride -- is read from the plan's record.
     for (int l = 1; l < L; l++) {
-        const int16_t* Rp = R + 8 * (l - 1);
-        const int16_t* Rl = R + 8 * l;
-        const int sxa = Rp[0] & ~3, sy0 = Rp[1], sstride = 4 * ((Rp[2] - sxa + 3) >> 2);
-        const int x0 = Rl[0], y0 = Rl[1], x1 = Rl[2], y1 = Rl[3];
-        const int ox0 = Rl[4], oy0 = Rl[5], ox1 = Rl[6], oy1 = Rl[7];
+        const PzRec rec = pz_rec(R + 8 * l, Cn + kPzRec * l);
+        const int x0 = rec.x0, y0 = rec.y0, x1 = rec.x1, y1 = rec.y1;
+        const int ox0 = rec.ox0, oy0 = rec.oy0, ox1 = rec.ox1, oy1 = rec.oy1;
+        const int nq = rec.nq, rc = rec.rc, sstride = rec.sstride, sxa = rec.sxa, sy0 = rec.sy0;
         const LevelGeom& g = lv[l];
+        const int xa = x0 & ~3, hn = y1 - y0, ostride = 4 * nq;
+        const QuadSplit sp = quad_split(rec, tid);
+        // Every active thread computes exactly rc rows, so the row loop's trip count is
+        // the workgroup's: the last group's run is moved up to end at the rectangle's last
+        // row, and the rows it then shares with the group above are written twice with
+        // the same bytes.  (An empty rectangle has hn = 0; gr * rc < hn implies gr < G.)
+        const bool act = sp.gr * rc < hn;
+        const int ra = min(sp.gr * rc, hn - rc);
+        // the first quad's taps and the first 8 rows' taps are loaded before the barrier:
+        // their latency hides in the wait for the previous level.  WIN: one record per
+        // column quad (orbx_geometry.cpp quad_taps), the tile's own for its first quad,
+        // whose columns left of x0 borrow x0's taps, and the level's for the others.
+        // !WIN: the columns' taps (sx0, sx1, a0, a1 as 4 x int16); columns outside
+        // [x0, x1) borrow the nearest column's.  Such bytes are computed but never read by
+        // the next level and never owned.
         const int16_t* xt = rtab + g.xtab_off;
-        const int xa = x0 & ~3;
-        const int nq = (x1 - xa + 3) >> 2, hn = y1 - y0, ostride = 4 * nq;
-        const QuadSplit sp = quad_split(nq, tid);
-        const int rc = (hn + sp.G - 1) / sp.G;
-        const int ra = sp.gr * rc, rb = min(hn, ra + rc);
-        const bool act = x1 > x0 && y1 > y0 && sp.gr < sp.G && ra < rb;
-        // the first quad's column taps (sx0, sx1, a0, a1 as 4 x int16) and the first 8
-        // rows' taps are loaded before the barrier: their latency hides in the wait for
-        // the previous level.  Columns outside [x0, x1) (quad widening) borrow the nearest
-        // column's taps (the quad's source span stays monotone): their bytes are computed
-        // but never read by the next level and never owned.
-        const int16_t* yt = rtab + g.ytab_off + 4 * (y0 + ra);
+        const uint32_t rec_off = 2u * (uint32_t)(pz_coff + (tile * L + l) * kPzRec + 8);
+        const uint32_t qtab = 2u * (uint32_t)g.qtab_off + (uint32_t)(2 * kPzQuadRec) * (uint32_t)(xa >> 2);
+        const uint32_t ytap = 2u * (uint32_t)(g.ytab_off + 4 * (y0 + ra));
         int2 xtp[4], yv[8];  // rtab is padded at the end: 8 rows' taps are always readable
-        if (act) {
+        uint4 qsel, qab;
+        int qc0;
+        auto load_quad_taps = [&](int qq) {
+            if constexpr (WIN) {
+                const uint32_t o = qq == 0 ? rec_off : qtab + (uint32_t)(2 * kPzQuadRec) * (uint32_t)qq;
+                qsel = ld_off<uint4>(rtab, o);
+                qab = ld_off<uint4>(rtab, o + 16);
+                qc0 = ld_off<int>(rtab, o + 32);
+            } else {
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int x = xa + 4 * sp.q + k;
-                xtp[k] = *(const int2*)(xt + 4 * min(max(x, x0), x1 - 1));
+                for (int k = 0; k < 4; k++)
+                    xtp[k] = *(const int2*)(xt + 4 * min(max(xa + 4 * qq + k, x0), x1 - 1));
             }
+        };
+        if (act) {
+            load_quad_taps(sp.q);
 #pragma unroll
-            for (int k = 0; k < 8; k++) yv[k] = *(const int2*)(yt + 4 * k);
+            for (int k = 0; k < 8; k++) yv[k] = ld_off<int2>(rtab, ytap + 8 * k);
         }
+        uint8_t* const gb = frame + g.off;
+        const int gpitch = g.pitch;
         __syncthreads();
+        // The taps are needed from here on: one wait for all of them (vmcnt(0); row runs
+        // under 8 rows never read the later ones).  With nothing left outstanding on any
+        // path, the next level's loads are issued without first waiting for this level's
+        // stores.
+        __builtin_amdgcn_s_waitcnt(0x0f70);
         if (!act) continue;
         const uint8_t* sb = s_pz + ((l & 1) ? 0 : lds_a);
         uint8_t* ob = s_pz + ((l & 1) ? lds_a : 0);
         // owned rows of this thread's run, relative to the rectangle
-        const int wlo = max(ra, oy0 - y0), whi = min(rb, oy1 - y0);
+        const int wlo = max(ra, oy0 - y0), whi = min(ra + rc, oy1 - y0);
         for (int qq = sp.q; qq < nq; qq += sp.nqp) {
             const int x = xa + 4 * qq;
             // 0: not owned, 1: whole quad owned, 2: partly owned
             const int own = (x + 4 <= ox0 || x >= ox1) ? 0 : ((x >= ox0 && x + 4 <= ox1) ? 1 : 2);
+            // owned rows of a wholly / partly owned quad (a part only at ownership boundaries)
+            const uint32_t nfull = own == 1 ? (uint32_t)max(whi - wlo, 0) : 0u;
+            const uint32_t npart = own == 2 ? (uint32_t)max(whi - wlo, 0) : 0u;
             if (qq != sp.q) {  // a second quad (rectangles over 1024 columns): reload
+                load_quad_taps(qq);
 #pragma unroll
-                for (int k = 0; k < 4; k++) xtp[k] = *(const int2*)(xt + 4 * min(max(x + k, x0), x1 - 1));
-#pragma unroll
-                for (int k = 0; k < 8; k++) yv[k] = *(const int2*)(yt + 4 * k);
+                for (int k = 0; k < 8; k++) yv[k] = ld_off<int2>(rtab, ytap + 8 * k);
+                __builtin_amdgcn_s_waitcnt(0x0f70);
             }
+            // WIN (the plan checked that every quad's source bytes span at most 8 and lie
+            // inside the staged rows): the row's bytes come from three aligned dwords,
+            // shifted to start at the first column's sx0 (two v_alignbyte); then per column
+            // one v_perm_b32 pairs bytes sx0, sx1 as u16 halves and one v_dot2_u32_u16
+            // with (a0, a1) gives h.
             int c0[4], c1[4];
             uint32_t a0[4], a1[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                c0[k] = (int16_t)(xtp[k].x & 0xffff) - sxa;
-                c1[k] = (int16_t)(xtp[k].x >> 16) - sxa;
-                a0[k] = (uint32_t)(xtp[k].y & 0xffff);
-                a1[k] = (uint32_t)xtp[k].y >> 16;
-            }
-            // WIN (the plan checked that every quad's source bytes c0[0] .. c1[3] span at
-            // most 8): the row's bytes come from three aligned dwords, shifted to start
-            // at c0[0] (two v_alignbyte); then per column one v_perm_b32 pairs bytes c0,
-            // c1 as u16 halves and one v_dot2_u32_u16 with (a0, a1) gives h.
-            const int wbase = c0[0] & ~3, wsh = c0[0] & 3;
+            int wofs = 0, wsh = 0;
             uint32_t wsel[4];
             ushort2_t wab[4];
+            if constexpr (WIN) {
+                wofs = (qc0 & ~3) - sxa - sy0 * sstride;
+                wsh = qc0 & 3;
+                wsel[0] = qsel.x, wsel[1] = qsel.y, wsel[2] = qsel.z, wsel[3] = qsel.w;
+                wab[0] = __builtin_bit_cast(ushort2_t, qab.x), wab[1] = __builtin_bit_cast(ushort2_t, qab.y);
+                wab[2] = __builtin_bit_cast(ushort2_t, qab.z), wab[3] = __builtin_bit_cast(ushort2_t, qab.w);
+            } else {
+                wofs = -sy0 * sstride;
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                wsel[k] = (uint32_t)(c0[k] - c0[0]) | 0x0c00u | ((uint32_t)(c1[k] - c0[0]) << 16) | 0x0c000000u;
-                wab[k] = ushort2_t{(unsigned short)a0[k], (unsigned short)a1[k]};
-            }
-            const int16_t* yp = yt;
-            uint8_t* lp = ob + ra * ostride + 4 * qq;
-            uint8_t* gp = frame + g.off + (size_t)(y0 + ra) * g.pitch + x;
-            int s_cur = -1;
-            const uint8_t* srow = sb;
-            uint32_t hc[4] = {0, 0, 0, 0}, hp[4] = {0, 0, 0, 0};
-            for (int rr = ra; rr < rb; rr += 8) {
-                if (rr != ra) {  // the next 8 rows' taps
-#pragma unroll
-                    for (int k = 0; k < 8; k++) yv[k] = *(const int2*)(yp + 4 * k);
+                for (int k = 0; k < 4; k++) {
+                    c0[k] = (int16_t)(xtp[k].x & 0xffff) - sxa;
+                    c1[k] = (int16_t)(xtp[k].x >> 16) - sxa;
+                    a0[k] = (uint32_t)(xtp[k].y & 0xffff);
+                    a1[k] = (uint32_t)xtp[k].y >> 16;
                 }
-                yp += 32;
+            }
+            // horizontal sums of one source row
+            auto hsum = [&](int row, uint32_t (&h)[4]) {
+                const uint8_t* srow = sb + (row * sstride + wofs);
+                if constexpr (WIN) {
+                    const uint32_t* wp = (const uint32_t*)srow;
+                    const uint32_t d0 = wp[0], d1 = wp[1], d2 = wp[2];
+                    const uint32_t lo = __builtin_amdgcn_alignbyte(d1, d0, wsh);
+                    const uint32_t hi = __builtin_amdgcn_alignbyte(d2, d1, wsh);
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const uint32_t pr = __builtin_amdgcn_perm(hi, lo, wsel[k]);
+                        h[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(ushort2_t, pr), wab[k], 0u, false) & ~15u;
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; k++)  // two byte reads (a merged u16 read would be unaligned)
+                        h[k] = (srow[c0[k]] * a0[k] + srow[c1[k]] * a1[k]) & ~15u;
+                }
+            };
+            uint32_t lofs = (uint32_t)(ra * ostride + 4 * qq);
+            uint32_t gofs = (uint32_t)((y0 + ra) * gpitch + x);
+            // An output row reads source rows r0 and r1 (r1 = r0 + 1, or r0 where the table
+            // clips at the level's last row), and r0 is never below the row before's r1
+            // (make_plan checks the tables): r1's sums always go to the register set that
+            // held the older row and r0's are computed only when r0 is past the newest
+            // row, so the two sets swap roles from one output row to the next instead of
+            // being copied, and a clipped row needs no special case.
+            int s_cur = -1;
+            uint32_t he[4] = {0, 0, 0, 0}, ho[4] = {0, 0, 0, 0};
+            for (int rr = 0; rr < rc; rr += 8) {
+                if (rr != 0) {  // the next 8 rows' taps
+#pragma unroll
+                    for (int k = 0; k < 8; k++) yv[k] = ld_off<int2>(rtab, ytap + 8 * (rr + k));
+                    __builtin_amdgcn_s_waitcnt(0x0f70);
+                }
 #pragma unroll
                 for (int kb = 0; kb < 8; kb++) {
-                    const int r = rr + kb;
-                    if (r >= rb) break;
+                    if (rr + kb >= rc) break;
+                    const int r = ra + rr + kb;
                     const int2 t = yv[kb];
                     const int r0 = (int16_t)(t.x & 0xffff), r1 = (int16_t)(t.x >> 16);
-                    while (s_cur < r1) {  // the source rows are monotone; each is summed once
-                        if (s_cur < 0) {
-                            s_cur = r0;
-                            srow = sb + (r0 - sy0) * sstride;
-                        } else {
-                            s_cur++;
-                            srow += sstride;
-                        }
-                        if constexpr (WIN) {
-#if ORBX_PZ_QWORD
-                            // two 8-byte aligned qword reads: a wave's 32-lane group then
-                            // spans ~19 qwords over LDS's 64 dword banks (conflict-free),
-                            // where three dword reads spread ~38 dwords over 32 banks
-                            // (pointer arithmetic only: an integer round trip would turn the
-                            // reads into flat loads)
-                            const uint8_t* pw = srow + wbase + wsh;
-                            const int mis = (int)((uintptr_t)pw & 7);
-                            const uint2* qp = (const uint2*)(pw - mis);
-                            const uint2 qa = qp[0];
-                            asm volatile("" ::: "memory");  // two ds_read_b64, not one ds_read2_b64 (8 cycles)
-                            const uint2 qb = qp[1];
-                            const bool hi4 = (mis & 4) != 0;
-                            const uint32_t e0 = hi4 ? qa.y : qa.x, e1 = hi4 ? qb.x : qa.y, e2 = hi4 ? qb.y : qb.x;
-                            const uint32_t lo = __builtin_amdgcn_alignbyte(e1, e0, (uint32_t)mis & 3);
-                            const uint32_t hi = __builtin_amdgcn_alignbyte(e2, e1, (uint32_t)mis & 3);
-#else
-                            const uint32_t* wp = (const uint32_t*)(srow + wbase);
-                            const uint32_t d0 = wp[0], d1 = wp[1], d2 = wp[2];
-                            const uint32_t lo = __builtin_amdgcn_alignbyte(d1, d0, wsh);
-                            const uint32_t hi = __builtin_amdgcn_alignbyte(d2, d1, wsh);
-#endif
-#pragma unroll
-                            for (int k = 0; k < 4; k++) {
-                                hp[k] = hc[k];
-                                const uint32_t pr = __builtin_amdgcn_perm(hi, lo, wsel[k]);
-                                hc[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(ushort2_t, pr), wab[k], 0u, false) &
-                                        ~15u;
-                            }
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < 4; k++) {
-                                hp[k] = hc[k];
-                                // two byte reads (a merged u16 read would be unaligned)
-                                hc[k] = (srow[c0[k]] * a0[k] + srow[c1[k]] * a1[k]) & ~15u;
-                            }
-                        }
-                    }
+                    uint32_t(&h0)[4] = (kb & 1) ? ho : he;
+                    uint32_t(&h1)[4] = (kb & 1) ? he : ho;
+                    if (r0 > s_cur) hsum(r0, h0);
+                    hsum(r1, h1);
+                    s_cur = r1;
                     const uint32_t b0 = ((uint32_t)t.y & 0xffffu) << 12, b1 = ((uint32_t)t.y >> 16) << 12;
-                    const bool same = r0 == s_cur;
                     uint32_t packed = 0;
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
-                        const uint32_t v = (mulhi24(b0, same ? hc[k] : hp[k]) + mulhi24(b1, hc[k]) + 2) >> 2;
+                        const uint32_t v = (mulhi24(b0, h0[k]) + mulhi24(b1, h1[k]) + 2) >> 2;
                         packed |= v << (8 * k);
                     }
-                    *(uint32_t*)lp = packed;
-                    if (own != 0 && r >= wlo && r < whi) {
-                        if (own == 1) *(uint32_t*)gp = packed;
-                        else
-                            store_owned_quad(gp, x, ox0, ox1, packed);
-                    }
-                    lp += ostride;
-                    gp += g.pitch;
+                    *(uint32_t*)(ob + lofs) = packed;
+                    if ((uint32_t)(r - wlo) < nfull) *(uint32_t*)(gb + gofs) = packed;
+                    if ((uint32_t)(r - wlo) < npart) store_owned_quad(gb + gofs, x, ox0, ox1, packed);
+                    lofs += ostride;
+                    gofs += gpitch;
                 }
             }
         }
@@ -2125,7 +2160,7 @@ hipError_t launch_extract(const Plan& plan, const DeviceBuffers& db, int batch, 
             const size_t fp = s == 0 ? frame_pitch : (size_t)fb, st = s == 0 ? stride : (size_t)g0.pitch;
             const int vec4 = ((uintptr_t)in % 4 == 0) && (st % 4 == 0) && (fp % 4 == 0);
             hipLaunchKernelGGL(kern, dim3(sg.tiles * batch), dim3(256), (size_t)sg.lds_a + sg.lds_b, stream, in, fp, st,
-                               vec4, db.pyr, fb, db.lv + sg.l0, sg.nl, db.rtab, sg.off, sg.tiles, batch, sg.lds_a,
+                               vec4, db.pyr, fb, db.lv + sg.l0, sg.nl, db.rtab, sg.off, sg.coff, sg.tiles, batch, sg.lds_a,
                                db.status, (s == 0 && l0) ? 0 : 1);
         }
     }

@@ -103,6 +103,27 @@ static void resize_tables(int sw, int sh, int dw, int dh, int16_t* xtab, int16_t
     }
 }
 
+// Tap record of k_pyramid<true> for the column quad x .. x + 3 of a resized level, columns
+// clamped to [lo, hi]: kPzQuadRec int16 (three 16-byte pieces) -- the four v_perm_b32
+// selectors that pair source bytes sx0, sx1 of each column (relative to the first
+// column's sx0) as u16 halves, the four (a0, a1) weight pairs, and the first column's sx0
+// (the start of the row's source window).  A clamped column borrows its neighbour's taps
+// (the quad's source span stays monotone): its byte is computed but never read by the
+// next level and never owned.
+static void quad_taps(const int16_t* xt, int x, int lo, int hi, int16_t* qt) {
+    const int c00 = xt[4 * std::min(std::max(x, lo), hi)];
+    for (int k = 0; k < 4; k++) {
+        const int16_t* t = xt + 4 * std::min(std::max(x + k, lo), hi);
+        // byte selectors hold only while pz_win's span check does (masked otherwise)
+        qt[2 * k] = (int16_t)(((t[0] - c00) & 7) | 0x0c00);
+        qt[2 * k + 1] = (int16_t)(((t[1] - c00) & 7) | 0x0c00);
+        qt[8 + 2 * k] = t[2];
+        qt[8 + 2 * k + 1] = t[3];
+    }
+    qt[16] = (int16_t)c00;
+    for (int k = 17; k < kPzQuadRec; k++) qt[k] = 0;
+}
+
 // k_pyramid tile rectangles (orbx_geometry.h).  Ownership: level 0 is split into an
 // nx x ny grid; a boundary b at level l - 1 moves to the first level-l column (row)
 // whose resize source starts at or after b, so a tile's owned pixels at level l read
@@ -111,6 +132,9 @@ static void resize_tables(int sw, int sh, int dw, int dh, int16_t* xtab, int16_t
 // resize tables' source footprints (the tables are monotone, so a range of columns
 // maps to [t(first).s0, t(last).s1]): the halo is 0 on the left / top and about
 // 1 + 1.2 * (halo of the level above) on the right / bottom.
+// Per (tile, level) one table holds the rectangles (8 int16) and a parallel one kPzRec
+// int16 (orbx_geometry.h): what every thread of the workgroup would otherwise derive
+// from the rectangles, and the tap record of the rectangle's first column quad.
 // One segment: levels s.l0 .. s.l0 + s.nl - 1, tiled over level s.l0 (owned by the
 // segment only when s.l0 == 0: a later segment's input level is already in HBM).
 static bool pyramid_segment(Plan& plan, PzSeg& s, int tw, int th) {
@@ -120,8 +144,11 @@ static bool pyramid_segment(Plan& plan, PzSeg& s, int tw, int th) {
     s.nx = nx;
     s.ny = ny;
     s.tiles = nx * ny;
+    plan.rtab.resize((plan.rtab.size() + 7) & ~(size_t)7);  // records are read as 16-byte pieces
     s.off = (int)plan.rtab.size();
     plan.rtab.resize(plan.rtab.size() + (size_t)nx * ny * n * 8);
+    s.coff = (int)plan.rtab.size();
+    plan.rtab.resize(plan.rtab.size() + (size_t)nx * ny * n * kPzRec);
     // owned boundaries per segment level: bx[k][0..nx], by[k][0..ny] (level l0 + k)
     std::vector<std::vector<int>> bx(n, std::vector<int>(nx + 1)), by(n, std::vector<int>(ny + 1));
     for (int j = 0; j <= nx; j++) bx[0][j] = (int)(((long long)j * g0.w) / nx);
@@ -144,6 +171,7 @@ static bool pyramid_segment(Plan& plan, PzSeg& s, int tw, int th) {
     for (int ty = 0; ty < ny; ty++)
         for (int tx = 0; tx < nx; tx++) {
             int16_t* R = plan.rtab.data() + s.off + (size_t)(ty * nx + tx) * n * 8;
+            int16_t* Cn = plan.rtab.data() + s.coff + (size_t)(ty * nx + tx) * n * kPzRec;
             int nx0 = 0, ny0 = 0, nx1 = 0, ny1 = 0;  // needed rectangle of level l + 1
             for (int k = n - 1; k >= 0; k--) {
                 const int l = l0 + k;
@@ -166,9 +194,30 @@ static bool pyramid_segment(Plan& plan, PzSeg& s, int tw, int th) {
                     any = true;
                 }
                 if (!any) x0 = x1 = y0 = y1 = 0;
+                // thread -> (column quad, row group) split of the rectangle (k_pyramid): G
+                // groups of min(nq, 256) lanes, rc rows each; tid / nqp = (tid * mul) >> 16
+                // for tid < 256 (mul = 65536 / nqp + 1 errs by under 256 / 65536 <= 1 / nqp)
+                const int nq = any ? (x1 - (x0 & ~3) + 3) >> 2 : 0, nqp = std::min(nq, 256);
+                const int G = any ? 256 / nqp : 0, rc = any ? (y1 - y0 + G - 1) / G : 0;
+                const int mul = any ? 65536 / nqp + 1 : 0;
                 const int16_t r[8] = {(int16_t)x0, (int16_t)y0, (int16_t)x1, (int16_t)y1,
                                       (int16_t)ox0, (int16_t)oy0, (int16_t)ox1, (int16_t)oy1};
                 std::memcpy(R + 8 * k, r, sizeof(r));
+                int16_t c[kPzRec] = {(int16_t)nq, (int16_t)G, (int16_t)rc, 0, 0, 0,
+                                     (int16_t)(mul & 0xffff), (int16_t)(mul >> 16)};
+                // the first quad starts at x0 & ~3, left of the rectangle when x0 is not on a
+                // quad: those columns borrow x0's taps, so the quad's source window starts
+                // inside the staged source rectangle (the level-wide records start theirs at
+                // the quad's own first column)
+                if (k >= 1 && any) quad_taps(plan.rtab.data() + plan.lv[l].xtab_off, x0 & ~3, x0, x1 - 1, c + 8);
+                std::memcpy(Cn + kPzRec * k, c, sizeof(c));
+                if (k + 1 < n) {  // this level's staged rectangle is the source of level k + 1
+                    int16_t* U = Cn + kPzRec * (k + 1);
+                    const int sxa = x0 & ~3;
+                    U[3] = (int16_t)(4 * nq);  // LDS row stride of the source
+                    U[4] = (int16_t)sxa;
+                    U[5] = (int16_t)y0;
+                }
                 // LDS holds the needed columns widened to whole 4-byte quads
                 // (+ 16: k_pyramid<true> reads a row's source window as three dwords, which
                 // can reach 8 bytes past the last row's last quad)
@@ -216,6 +265,35 @@ static bool pyramid_tiles(Plan& plan) {
         const int16_t* xt = plan.rtab.data() + g.xtab_off;
         for (int x = 0; x < g.w; x++)
             if (xt[4 * std::min(x + 3, g.w - 1) + 1] - xt[4 * x] > 7) { plan.pz_win = false; break; }
+    }
+    // Level-wide quad tap records (quad_taps), one per aligned column quad x = 4 q of every
+    // resized level; columns past the level's width borrow the last column's taps.
+    for (int l = 1; l < L; l++) {
+        LevelGeom& g = plan.lv[l];
+        const int nqd = (g.w + 3) / 4;
+        plan.rtab.resize((plan.rtab.size() + 7) & ~(size_t)7);
+        g.qtab_off = (int)plan.rtab.size();
+        plan.rtab.resize(plan.rtab.size() + (size_t)nqd * kPzQuadRec, 0);
+        for (int q = 0; q < nqd; q++)
+            quad_taps(plan.rtab.data() + g.xtab_off, 4 * q, 0, g.w - 1, plan.rtab.data() + g.qtab_off + (size_t)q * kPzQuadRec);
+    }
+    // A rectangle's first quad takes the tile's own record, the others the level-wide ones
+    // (their first column lies inside the rectangle).  The window form also needs every
+    // quad's three-dword source window inside the staged source rectangle's rows plus
+    // their 8 bytes of slack.
+    for (int s = 0; s < plan.pz_nseg && plan.pz_win; s++) {
+        const PzSeg& sg = plan.pz[s];
+        for (int t = 0; t < sg.tiles * sg.nl && plan.pz_win; t++) {
+            const int16_t* R = plan.rtab.data() + sg.off + (size_t)t * 8;
+            const int16_t* Cn = plan.rtab.data() + sg.coff + (size_t)t * kPzRec;
+            if (t % sg.nl == 0 || Cn[0] == 0) continue;
+            const int16_t* qt = plan.rtab.data() + plan.lv[sg.l0 + t % sg.nl].qtab_off;
+            for (int q = 0; q < Cn[0]; q++) {
+                const int c00 = q == 0 ? Cn[8 + 16] : qt[(size_t)((R[0] >> 2) + q) * kPzQuadRec + 16];
+                const int wb = (c00 & ~3) - Cn[4];
+                if (wb < 0 || wb + 12 > Cn[3] + 8) { plan.pz_win = false; break; }
+            }
+        }
     }
     return true;
 }
@@ -329,6 +407,11 @@ bool make_plan(Plan& plan, const OrbParams& prm, int W, int H) {
             g.ytab_off = (int)plan.rtab.size();
             plan.rtab.resize(plan.rtab.size() + 4 * (size_t)g.h);
             resize_tables(prev_w, prev_h, g.w, g.h, plan.rtab.data() + g.xtab_off, plan.rtab.data() + g.ytab_off);
+            // k_pyramid's row walk: a level is never taller than its source, so an output
+            // row's first source row is at or past the row before's second
+            const int16_t* yt = plan.rtab.data() + g.ytab_off;
+            for (int y = 1; y < g.h; y++)
+                if (yt[4 * y] < yt[4 * (y - 1) + 1]) { plan.why = "resize rows do not advance"; return false; }
         }
         prev_w = g.w;
         prev_h = g.h;

@@ -46,7 +46,7 @@ bool init_params(OrbParams& p, int nfeatures, float scale_factor, int nlevels, i
 struct LevelGeom {
     int w, h;              // ROI size
     int pitch;             // row pitch (bytes) of this level in the pyramid/blur buffers
-    int pad0;
+    int qtab_off;          // k_pyramid<true>'s quad tap records (int16 units into the resize table buffer; levels >= 1)
     long long off;         // byte offset of the level inside one frame's pyramid block
     // FAST cells
     int cell_first, ncells;
@@ -85,6 +85,14 @@ struct CellGeom {
 // plus the source footprint of its needed rectangle at level l + 1, so levels chain
 // inside LDS with a small recomputed right / bottom halo.  Per (tile, level) the table
 // holds 8 int16: needed x0, y0, x1, y1 and owned x0, y0, x1, y1 (ends exclusive).
+// A parallel table holds, per (tile, level), kPzRec int16 that the kernel's threads
+// would all derive from them: [0] nq, the rectangle's width in column quads from
+// x0 & ~3; [1] G = 256 / min(nq, 256) row groups; [2] rc = ceil(rows / G) rows per group;
+// [3] the LDS row stride, [4] x0 & ~3 and [5] y0 of the level below (the resize source);
+// [6], [7] the low and high half of the multiplier that splits a thread id into (row
+// group, quad): tid / min(nq, 256) = (tid * mul) >> 16; [8 ..] the tap record of the
+// rectangle's first column quad (k_pyramid<true>, levels >= 1).  An empty rectangle has
+// zeros there.
 // Deep pyramids are built in segments of at most kPzSegLevels levels, one launch each:
 // a segment after the first takes its input level (the previous segment's last, already
 // in HBM) as its "level 0" and owns none of it.  Each segment's halo then grows over at
@@ -97,11 +105,14 @@ constexpr int kPzTW2 = 64, kPzTH2 = 48;
 constexpr int kPzSegLevels = 8;
 constexpr int kPzMaxSegs = kMaxLevels;
 constexpr int kPzMaxLds = 150 * 1024;
+constexpr int kPzQuadRec = 24;           // int16 per column-quad tap record: 4 selectors, 4 weight pairs, sx0, padding
+constexpr int kPzRec = 8 + kPzQuadRec;   // int16 per (tile, level) record of the parallel table
 
 struct PzSeg {
     int l0 = 0, nl = 0;           // input level and level count (l0 .. l0 + nl - 1)
     int nx = 0, ny = 0, tiles = 0;  // tile grid over level l0
     int off = 0;                  // offset (int16 units) of the tile rectangles in rtab
+    int coff = 0;                 // offset (int16 units) of the parallel table of per-(tile, level) constants
     int lds_a = 0, lds_b = 0;     // LDS ping / pong buffers (even / odd levels of the segment), bytes
 };
 
@@ -118,7 +129,8 @@ struct Plan {
     int tiles_total = 0;            // blur tiles per frame
     int pz_nseg = 0;                // k_pyramid segments (launches)
     PzSeg pz[kPzMaxSegs];
-    bool pz_win = false;            // k_pyramid<true>: every 4 columns' resize taps span <= 8 source bytes
+    bool pz_win = false;            // k_pyramid<true>: every 4 columns' resize taps span <= 8 source bytes, and the
+                                    // quad tap records' source windows lie inside every staged rectangle
     int fc_wr = 0, fc_wc = 0;       // largest FAST detection window (rows, cols)
     int max_ncap = 0;
     // describe in level-tile order (k_describe_tiles, bins from k_octree) instead of
