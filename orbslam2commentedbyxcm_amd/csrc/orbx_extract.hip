@@ -761,36 +761,54 @@ __global__ __launch_bounds__(256) void k_level_tiles(const uint8_t* __restrict__
 // in-window neighbour's M (a neighbour with M_n >= M_p > t always suppresses; one below
 // M_p never does) -- threshold-independent apart from M_p > t.  M is sparse (k_level_tiles
 // zeroes M <= min(iniTh, minTh)), so the wave stages the window with a zero frame, lists
-// the non-zero pixels in raster order (one ballot per row -- per row pair when the window
-// is at most 32 wide), tests only those against their neighbours, and writes the
-// survivors of the chosen threshold in the same order.
-// Staged window row pitch: 68 bytes (64 + zero frame, an odd dword count), a compile-time
-// constant.  Measured alternatives (ORBX_FC_PITCH): 44-100 bytes all slower at configs[4]
-// (up to -8 %, r05al / r05am), and a pitch sized to the widest window (36 bytes at 30-px
-// cells, 4.4 KB less LDS per workgroup) -6 % there (r05ac).  Passing the pitch at run
-// time (as that experiment did) cost configs[1] 1.1 % by itself (r05bh).
-#ifndef ORBX_FC_PITCH
-#define ORBX_FC_PITCH 68
-#endif
-constexpr int kFcStride = ORBX_FC_PITCH;
-#ifndef ORBX_FC_INFLIGHT
-#define ORBX_FC_INFLIGHT 8  // k_fast_cells: row steps of byte loads in flight (r05aw: 4 -2 %,
-                            // 16 -10 % at configs[1])
-#endif
-static_assert(kFcStride % 4 == 0 && kFcStride >= 36, "fast_cells window pitch");
+// the non-zero pixels in raster order, tests only those against their neighbours, and
+// writes the survivors of the chosen threshold in the same order.
+//
+// Staging.  The window is read as aligned dwords: lane = (row lane >> 4, dword lane & 15),
+// so one wave load covers 4 rows of the 64 bytes from the window's origin aligned down
+// to 4 (CellGeom::src_al; make_plan checks that the window and its right frame column fit
+// them).  All ceil(wr / 4) loads of a window of up to 40 rows are issued before the first
+// wait; a taller one (kCellMax) takes a second batch.  Lanes past the window's last dword
+// load nothing (the line requests they would add cost 5 % of the kernel); the others
+// load unclamped: the last load reads up to 3 rows past the window, and a row's dwords
+// end at most 64 bytes from its aligned start; make_plan checks for every cell that all
+// of it lies inside the level's block of the frame, and the launcher that the buffer and
+// the frame blocks are dword aligned.  Each lane's byte mask (left edge, right edge, and
+// for the last load "row >= wr") is built once from the cell's fields.
+// LDS rows are kFcStride = 68 bytes: one zero dword, then the 16 staged dwords, so M(r, c)
+// sits at (r + 1) * 68 + 4 + (src_off & 3) + c.  Column -1 is the zero dword or a masked
+// byte, column wc a masked byte; rows -1 and wr are zeroed by one store, and the last
+// load's rows past the window store their (masked, zero) dwords into row wr.
+// Listing.  Candidates are listed from the staged rows with one ballot per row (per row
+// pair for windows up to 32 wide), lane = column: raster order by construction.  Listing
+// from the dwords themselves (a wave prefix over per-lane byte counts per load, or a list
+// of non-zero dwords expanded afterwards) was built and measured slower: DESIGN.md
+// section 5, round 9.  A pixel is a candidate iff M > tc = max(min(ti, tm), 1): at
+// min(ti, tm) = 0 the map keeps M = 1, which is none.
+// Both loops are written for the scalar unit as much as for the vector one: the kernel
+// issues about as many scalar as vector instructions, and the per-step tests and
+// branches of the generic loops cost more than the loads they guard (section 5).
+// The pitch is a compile-time constant (passing it at run time cost configs[1] 1.1 % by
+// itself, r05bh; DESIGN.md section 5 has the pitches measured with the byte layout).
+constexpr int kFcStride = 4 + kFcSpan;
+constexpr int kFcBatch = 10;  // loads in flight: 40 rows
+static_assert(kFcRows * 16 == 64 && kFcSpan == 64, "k_fast_cells lane layout");
 
 __global__ __launch_bounds__(256) void k_fast_cells(const uint8_t* __restrict__ score, long long fb,
                                                     const CellGeom* __restrict__ cells, int ncells,
                                                     int ini_th, int min_th, uint32_t* __restrict__ slots,
-                                                    int slots_pf, int* __restrict__ cell_count, int nframes,
-                                                    int max_wr, int max_wc) {
-    // per wave: (max_wr + 2) framed rows of M (pitch kFcStride >= max_wc + 2, checked by
-    // the launcher), then a candidate list of max_wr*max_wc u16
+                                                    int slots_pf, int* __restrict__ cell_count, int xcd,
+                                                    int per_frame, uint32_t pf_mul, int max_wr, int max_wc) {
+    // per wave: (max_wr + 2) framed rows of M, then a candidate list of max_wr*max_wc u16
     extern __shared__ __align__(16) uint8_t s_dyn[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int per_wave = (((max_wr + 2) * kFcStride + 2 * max_wr * max_wc) + 15) & ~15;
-    int f, cb;
-    xcd_frame_block((ncells + 3) / 4, nframes, f, cb);
+    // xcd_frame_block's map with the division by per_frame as a multiplication
+    // (fc_div_mul, orbx_geometry.h; exact for every id of the grid, checked by the launcher)
+    const uint32_t lin = blockIdx.x, k = xcd ? lin / kXcds : lin;
+    const int fl = (int)(((unsigned long long)k * pf_mul) >> 31);
+    const int cb = (int)k - fl * per_frame;
+    const int f = xcd ? fl * kXcds + (int)(lin % kXcds) : fl;
     const int ci = cb * 4 + wave;
     if (ci >= ncells) return;  // whole wave exits; no block barriers below
     const CellGeom c = cells[ci];
@@ -800,63 +818,122 @@ __global__ __launch_bounds__(256) void k_fast_cells(const uint8_t* __restrict__ 
         const int ti = ini_th < 0 ? 0 : (ini_th > 255 ? 255 : ini_th);
         const int tm = min_th < 0 ? 0 : (min_th > 255 ? 255 : min_th);
         const int tc = max(min(ti, tm), 1);  // candidates: M > tc
-        const uint8_t* src = score + (size_t)f * fb + c.src_off;
-        uint8_t* m = s_dyn + wave * per_wave;  // m[(r + 1) * kFcStride + c + 1] = M(r, c)
+        const uint8_t* src = score + (size_t)f * fb + c.src_al;
+        uint8_t* m = s_dyn + wave * per_wave;
         uint16_t* list = (uint16_t*)(s_dyn + wave * per_wave + (max_wr + 2) * kFcStride);
         const unsigned long long below = (1ull << lane) - 1;
-        // zero frame: rows -1 and wr, column -1 (column wc is written as 0 below)
-        for (int i = lane; i < kFcStride; i += 64) {
-            m[i] = 0;
-            m[(wr + 1) * kFcStride + i] = 0;
-        }
-        for (int r = lane; r < wr + 2; r += 64) {  // columns -1 and wc
-            m[r * kFcStride] = 0;
-            m[r * kFcStride + wc + 1] = 0;
-        }
-        int n = 0;
-        const bool pairs = wc <= 32;
-        const int col = pairs ? (lane & 31) : lane;
-        const int half = pairs ? (lane >> 5) : 0;
-        const int rstep = pairs ? 2 : 1;
-        const bool act = col < wc;
-        // 8 row steps of loads in flight at a time.  The loads are unconditional: the
-        // window ends >= 19 rows above the level's bottom and rows are >= 64 wide, so up
-        // to 15 rows / 63 columns past it stay inside the frame's block (and the buffer
-        // has slack); the values are masked.  The row part of each offset is wave-uniform
-        // (scalar adds to the base), the lane part a 32-bit vector offset.
-        const uint32_t loff = (uint32_t)(half * c.pitch + col);
-        constexpr int kIF = ORBX_FC_INFLIGHT;  // row steps of loads in flight
-        for (int r0 = 0; r0 < wr; r0 += kIF * rstep) {
-            int v[kIF];
+        const int q = lane & 15, rl = lane >> 4;
+        const int a = c.src_off & 3;
+        const uint8_t* mw = m + kFcStride + 4 + a;  // mw[r * kFcStride + c] = M(r, c)
+        // zero frame: rows -1 and wr (17 dwords each), and the zero dword of rows 0 .. wr-1
+        if (lane < 34) *(uint32_t*)(m + (lane < 17 ? 4 * lane : (wr + 1) * kFcStride + 4 * (lane - 17))) = 0u;
+        if (lane < wr) *(uint32_t*)(m + (lane + 1) * kFcStride) = 0u;
+        // this lane's byte mask, and the same for the last load (its rows past the window
+        // are masked whole and stored into row wr, which is zero anyway)
+        const int nl = (wr + kFcRows - 1) / kFcRows;
+        const bool row_in = rl < wr - kFcRows * (nl - 1);
+        uint32_t mk = q > c.last_q ? 0u : 0xffffffffu;
+        mk &= q == 0 ? c.first_mask : 0xffffffffu;
+        mk &= q == c.last_q ? c.last_mask : 0xffffffffu;
+        const uint32_t mk_last = row_in ? mk : 0u;
+        const uint32_t st = (uint32_t)((rl + 1) * kFcStride + 4 + 4 * q);  // load k: + k * 4 rows
+        const uint32_t st_last = row_in ? st + (uint32_t)((nl - 1) * kFcRows * kFcStride)
+                                        : (uint32_t)((wr + 1) * kFcStride + 4 + 4 * q);
+        // The row part of each address is wave-uniform (scalar adds to the base), the lane
+        // part a 32-bit vector offset.  Lanes past the window's last dword load nothing.
+        // A window of up to kFcBatch loads (40 rows) runs the form unrolled for its count:
+        // no per-load tests, and which load is the last is known at compile time.
+        const uint32_t loff = (uint32_t)(rl * c.pitch + 4 * q);
+        const size_t lstep = (size_t)(kFcRows * c.pitch);
+        const bool ld_lane = q <= c.last_q;
+        auto stage = [&](auto nl_t) {
+            constexpr int NL = decltype(nl_t)::value;
+            uint32_t v[NL];
 #pragma unroll
-            for (int k = 0; k < kIF; k++) {
-                // more than 8 steps: rows clamped to the window (at most one row past it)
-                const int rk = kIF > 8 ? min(r0 + k * rstep, wr - 1) : r0 + k * rstep;
-                v[k] = src[(uint32_t)(rk * c.pitch) + loff];
+            for (int k = 0; k < NL; k++) v[k] = 0u;
+            if (ld_lane) {
+#pragma unroll
+                for (int k = 0; k < NL; k++) v[k] = ld_off<uint32_t>(src + (size_t)k * lstep, loff);
             }
 #pragma unroll
-            for (int k = 0; k < kIF; k++) v[k] = (act && r0 + k * rstep + half < wr) ? v[k] : 0;
+            for (int k = 0; k < NL - 1; k++) *(uint32_t*)(m + st + (uint32_t)(k * kFcRows * kFcStride)) = v[k] & mk;
+            *(uint32_t*)(m + st_last) = v[NL - 1] & mk_last;
+        };
+        switch (nl) {
+            case 1: stage(std::integral_constant<int, 1>{}); break;
+            case 2: stage(std::integral_constant<int, 2>{}); break;
+            case 3: stage(std::integral_constant<int, 3>{}); break;
+            case 4: stage(std::integral_constant<int, 4>{}); break;
+            case 5: stage(std::integral_constant<int, 5>{}); break;
+            case 6: stage(std::integral_constant<int, 6>{}); break;
+            case 7: stage(std::integral_constant<int, 7>{}); break;
+            case 8: stage(std::integral_constant<int, 8>{}); break;
+            case 9: stage(std::integral_constant<int, 9>{}); break;
+            case 10: stage(std::integral_constant<int, 10>{}); break;
+            default:  // taller than 40 rows: batches, each load tested
+                for (int k0 = 0; k0 < nl; k0 += kFcBatch) {
+                    uint32_t v[kFcBatch];
 #pragma unroll
-            for (int k = 0; k < kIF; k++) {
-                const int rb = r0 + k * rstep;  // first row of this step (wave-uniform)
-                if (rb < wr) {
-                    const int r = rb + half;
-                    // (a pitch of at least 65 holds every lane's column; a smaller one only
-                    // the window and its right frame)
-                    if (r < wr && (kFcStride >= 65 || col <= wc)) m[(r + 1) * kFcStride + col + 1] = (uint8_t)v[k];
-                    const unsigned long long b = __ballot(v[k] > tc);  // raster order: row rb, then rb+1
-                    if ((b >> lane) & 1ull) list[n + __popcll(b & below)] = (uint16_t)((r << 8) | col);
-                    n += __popcll(b);
+                    for (int k = 0; k < kFcBatch; k++) v[k] = 0u;
+                    if (ld_lane) {
+#pragma unroll
+                        for (int k = 0; k < kFcBatch; k++)
+                            if (k0 + k < nl) v[k] = ld_off<uint32_t>(src + (size_t)(k0 + k) * lstep, loff);
+                    }
+#pragma unroll
+                    for (int k = 0; k < kFcBatch; k++) {
+                        const int kk = k0 + k;  // wave-uniform
+                        if (kk < nl) {
+                            const bool last = kk == nl - 1;
+                            *(uint32_t*)(m + (last ? st_last : st + (uint32_t)(kk * kFcRows * kFcStride))) = v[k] & (last ? mk_last : mk);
+                        }
+                    }
                 }
-            }
         }
+        wave_lds_fence();
+        // The list, in raster order: one ballot per row of the staged window, lane = column
+        // (per row pair when the window is at most 32 wide: lanes 32-63 take the second
+        // row, which is the zero row wr when wr is odd).  Lanes past the window read its
+        // zero column wc.  The staged bytes carry their masks already, so a step is one LDS
+        // byte read at an immediate offset, the ballot and the list store; a lane without a
+        // candidate stores into the two bytes at the head of row -1, which nothing reads
+        // (the first byte read there is column -1 at offset 3 + (src_off & 3)), so the
+        // store needs no branch.  Steps run four at a time without tests while four remain.
+        int n = 0;
+        auto list_rows = [&](auto pairs_t) {
+            constexpr bool pairs = decltype(pairs_t)::value;
+            constexpr int rstep = pairs ? 2 : 1, kSteps = 4;
+            const int col = pairs ? (lane & 31) : lane, half = pairs ? (lane >> 5) : 0;
+            const uint8_t* pb = mw + half * kFcStride + min(col, wc);
+            const int rc_lane = (half << 8) | col;
+            auto step = [&](int u, int rb) {
+                const bool cand = u > tc;
+                const unsigned long long b = __ballot(cand);
+                const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, (uint32_t)n));
+                *(cand ? list + pos : (uint16_t*)m) = (uint16_t)(rc_lane + (rb << 8));
+                n += __popcll(b);
+            };
+            int r0 = 0;
+            for (; r0 + (kSteps - 1) * rstep < wr; r0 += kSteps * rstep) {
+                int u[kSteps];
+#pragma unroll
+                for (int k = 0; k < kSteps; k++) u[k] = pb[(r0 + k * rstep) * kFcStride];
+#pragma unroll
+                for (int k = 0; k < kSteps; k++) step(u[k], r0 + k * rstep);
+            }
+            for (; r0 < wr; r0 += rstep) step(pb[r0 * kFcStride], r0);
+        };
+        if (wc <= 32)
+            list_rows(std::true_type{});
+        else
+            list_rows(std::false_type{});
         wave_lds_fence();
         // neighbour test of the candidates (zero frame: no bounds checks), both thresholds
         auto keep_of = [&](int i, int& r, int& cc, int& M) -> bool {
             const int rc = list[i];
             r = rc >> 8;
             cc = rc & 255;
-            const uint8_t* p = m + (r + 1) * kFcStride + cc + 1;
+            const uint8_t* p = mw + r * kFcStride + cc;
             M = p[0];
             const int nb = max(max(max(p[-kFcStride - 1], p[-kFcStride]), max(p[-kFcStride + 1], p[-1])),
                                max(max(p[1], p[kFcStride - 1]), max(p[kFcStride], p[kFcStride + 1])));
@@ -901,7 +978,7 @@ __global__ __launch_bounds__(256) void k_fast_cells(const uint8_t* __restrict__ 
                         const int rc = list[i0 + lane];
                         r = rc >> 8;
                         cc = rc & 255;
-                        M = m[(r + 1) * kFcStride + cc + 1];
+                        M = mw[r * kFcStride + cc];
                     }
                 } else if (i0 + lane < n) {
                     keep = keep_of(i0 + lane, r, cc, M) && M > t;
@@ -2176,12 +2253,20 @@ hipError_t launch_extract(const Plan& plan, const DeviceBuffers& db, int batch, 
     if (ev && ev[2]) (void)hipEventRecord(ev[2], stream);
     if (stage_ev && stage_after == 2) (void)hipEventRecord(stage_ev, stream);
     for (int rep = 0; rep < (dup == 3 ? 2 : 1); rep++) {
-        dim3 grid(((ncells + 3) / 4) * batch);
-        if (plan.fc_wc + 2 > kFcStride) return hipErrorInvalidValue;  // a window wider than the staged pitch
+        // one workgroup per 4 cells; the kernel splits its id by per_frame with fc_div_mul's
+        // multiplier (orbx_geometry.h), exact up to the grid's last id
+        const int per_frame = (ncells + 3) / 4;
+        if (per_frame == 0) break;
+        const long long nwg = (long long)per_frame * batch;
+        if (!fc_div_exact(nwg - 1, per_frame)) return hipErrorInvalidValue;
+        // dword loads of the strength map: make_plan aligned every cell's offset within a
+        // frame block (and bounded what the loads reach); the base and the blocks must be too
+        if ((uintptr_t)db.score % 4 != 0 || fb % 4 != 0) return hipErrorInvalidValue;
+        dim3 grid((unsigned)nwg);
         const size_t fc_lds = 4 * (size_t)((((plan.fc_wr + 2) * kFcStride + 2 * plan.fc_wr * plan.fc_wc) + 15) & ~15);
         hipLaunchKernelGGL(k_fast_cells, grid, dim3(256), fc_lds, stream, db.score, fb, db.cells, ncells,
-                           plan.prm.ini_th, plan.prm.min_th, db.slots, plan.slots_per_frame, db.cell_count, batch,
-                           plan.fc_wr, plan.fc_wc);
+                           plan.prm.ini_th, plan.prm.min_th, db.slots, plan.slots_per_frame, db.cell_count,
+                           batch % kXcds == 0 ? 1 : 0, per_frame, fc_div_mul(per_frame), plan.fc_wr, plan.fc_wc);
     }
     if (ev && ev[3]) (void)hipEventRecord(ev[3], stream);
     if (stage_ev && stage_after == 3) (void)hipEventRecord(stage_ev, stream);

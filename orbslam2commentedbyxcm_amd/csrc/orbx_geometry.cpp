@@ -366,6 +366,24 @@ bool make_plan(Plan& plan, const OrbParams& prm, int W, int H) {
                 plan.fc_wr = std::max(plan.fc_wr, wr);
                 plan.fc_wc = std::max(plan.fc_wc, wc);
                 c.src_off = (int)(g.off + (long long)(c.y0 + 3) * g.pitch + c.x0 + 3);
+                if (wc > 0 && wr > 0) {
+                    // k_fast_cells' dword staging: g.off and g.pitch are multiples of 4, so the
+                    // window's rows all start a = src_off & 3 bytes into an aligned dword
+                    const int a = c.src_off & 3, last = a + wc - 1;
+                    if (a + wc > kFcSpan) { plan.why = "FAST cell window spans more than 16 aligned dwords"; return false; }
+                    c.src_al = c.src_off - a;
+                    c.first_mask = 0xffffffffu << (8 * a);
+                    c.last_q = last >> 2;
+                    c.last_mask = 0xffffffffu >> (8 * (3 - (last & 3)));
+                    // the last load reads up to 3 rows past the window, every row 64 bytes
+                    // from its aligned start (into the next row of the level when the window
+                    // lies at its right end): all of it inside this level's block
+                    const int nl = (wr + kFcRows - 1) / kFcRows;
+                    if ((long long)c.src_al + (long long)(kFcRows * nl - 1) * g.pitch + kFcSpan > g.off + (long long)g.pitch * g.h) {
+                        plan.why = "FAST cell loads reach past the level";
+                        return false;
+                    }
+                }
                 slot_off += c.slot_cap;
                 level_cap += c.slot_cap;
                 plan.cells.push_back(c);

@@ -77,7 +77,25 @@ struct CellGeom {
     int slot_cap;
     int src_off;           // level.off + (y0 + 3) * pitch + x0 + 3: detection window origin in a frame block
     int pitch;             // level row pitch
+    // k_fast_cells stages the window as aligned dwords, 16 per row from src_al (64 bytes:
+    // make_plan checks that every window fits, and that the rows the last load reads past
+    // the window lie inside the level).  Dword q of a row holds window columns
+    // 4 q - (src_off & 3) + {0..3}; these masks keep the bytes inside [0, cols - 6).
+    int src_al;            // src_off & ~3
+    uint32_t first_mask;   // byte mask of dword 0
+    int last_q;            // index of the last dword that holds a window column
+    uint32_t last_mask;    // its byte mask (dwords between the two are whole; if last_q == 0 both apply)
 };
+
+// Rows per k_fast_cells load (64 lanes = 4 rows x 16 dwords) and the bytes a row's 16 lanes cover.
+constexpr int kFcRows = 4, kFcSpan = 64;
+// The division of k_fast_cells' workgroup id by the plan's workgroups per frame d >= 1 as
+// (id * mul) >> 31 with mul = floor(2^31 / d) + 1: mul * d = 2^31 + e with 0 < e <= d, so
+// id * mul / 2^31 = id / d + id * e / (d * 2^31), whose floor is floor(id / d) whenever
+// id * e < 2^31 (the fraction of id / d is at most (d - 1) / d).  id * d < 2^31 suffices;
+// fc_div_exact is that condition and the launcher checks it for its last workgroup id.
+inline uint32_t fc_div_mul(int d) { return (uint32_t)((1ull << 31) / (unsigned)d) + 1u; }
+inline bool fc_div_exact(long long max_id, int d) { return max_id * d < (1ll << 31); }
 
 // k_pyramid: one workgroup per (frame, tile) computes every level of its tile.  A
 // tile owns a rectangle of every level (kPzTW x kPzTH at level 0, boundaries carried up
