@@ -16,28 +16,12 @@
 #include <vector>
 
 #include "orbx.h"
-#include "orbx_error.h"
+#include "orbx_host.h"
 #include "orbx_kernels.h"
 
 using namespace orbx;
 
 namespace {
-
-int fail(int code, const char* what) {
-    set_last_error(what ? what : "");
-    return code;
-}
-
-int hip_fail(hipError_t e, const char* where) {
-    set_last_error(std::string(where) + ": " + hipGetErrorString(e));
-    return ORBX_ERR_HIP;
-}
-
-#define HIP_TRY(expr)                                      \
-    do {                                                   \
-        hipError_t _e = (expr);                            \
-        if (_e != hipSuccess) return hip_fail(_e, #expr);  \
-    } while (0)
 
 template <typename T>
 hipError_t dalloc(T** p, size_t n) {
@@ -577,10 +561,10 @@ int orbx_extract_batch_device(orbx_extractor* ex, int batch, const uint8_t* d_im
 
 namespace {
 // Scoped: the enclosing host call's wall time into ex->last_call_us.
-struct CallClock {
+struct ExtractorClock {
     orbx_extractor* ex;
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    ~CallClock() {
+    ~ExtractorClock() {
         if (ex) ex->last_call_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     }
 };
@@ -590,7 +574,7 @@ double orbx_extractor_last_call_us(const orbx_extractor* ex) { return ex ? ex->l
 
 int orbx_extract_batch(orbx_extractor* ex, int batch, const uint8_t* const* imgs, int width, int height,
                        size_t stride, orbx_keypoint* kps, uint8_t* desc, int cap, int* n_per_frame) {
-    CallClock clock{ex};
+    ExtractorClock clock{ex};
     if (!ex || batch < 0 || cap < 0 || !imgs) return fail(ORBX_ERR_ARG, "bad argument");
     if (batch == 0) return ORBX_OK;
     if (width <= 0 || height <= 0) return ORBX_EMPTY;

@@ -20,7 +20,7 @@
 
 #include "orbx.h"
 #include "orbx_block_sort.h"
-#include "orbx_error.h"
+#include "orbx_host.h"
 #include "orbx_match_types.h"
 
 using namespace orbx;
@@ -364,20 +364,6 @@ __global__ __launch_bounds__(kLastFrameThreads) void k_update_last_frame(LastFra
 }  // namespace orbx
 
 namespace {
-
-int fail(int code, const char* what) {
-    set_last_error(what);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                               \
-    do {                                                                            \
-        hipError_t _e = (expr);                                                     \
-        if (_e != hipSuccess) {                                                     \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));      \
-            return ORBX_ERR_HIP;                                                    \
-        }                                                                           \
-    } while (0)
 
 CamDev cam_dev(const orbx_camera* c) {
     CamDev C;

@@ -43,7 +43,6 @@
 // outputs are rounded to float once.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -53,14 +52,11 @@
 #include <vector>
 
 #include "orbx.h"
-#include "orbx_error.h"
+#include "orbx_host.h"
 #include "orbx_jacobi4.h"
 
 namespace orbx {
 
-int matcher_device(const orbx_matcher* m);  // orbx_matcher.cpp
-hipStream_t matcher_stream(const orbx_matcher* m);
-void matcher_set_last_call_us(orbx_matcher* m, double us);
 
 constexpr int kInitThreads = 256;
 constexpr int kInitWaves = kInitThreads / 64;
@@ -927,30 +923,13 @@ struct orbx_initializer {
     int device = 0, max_batch = 0, kcap = 0, max_iterations = 0;
     hipStream_t stream = nullptr;  // the matcher's
     char* work = nullptr;
-    char* stage = nullptr;         // the single host form's pair and results
-    size_t stage_cap = 0;
+    orbx::DeviceBuffer stage;      // the single host form's pair and results
     orbx::InitWork W{};
 };
 
 namespace {
 
 using namespace orbx;
-
-int fail(int code, const char* what) {
-    set_last_error(what);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                               \
-    do {                                                                            \
-        hipError_t _e = (expr);                                                     \
-        if (_e != hipSuccess) {                                                     \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));      \
-            return ORBX_ERR_HIP;                                                    \
-        }                                                                           \
-    } while (0)
-
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // the argument checks of both forms, before any GPU work
 int check_batch(const orbx_initializer* s, const orbx_initializer_batch* in) {
@@ -962,11 +941,6 @@ int check_batch(const orbx_initializer* s, const orbx_initializer_batch* in) {
         return fail(ORBX_ERR_ARG, "null buffer");
     return ORBX_OK;
 }
-
-// the fixed layout of the single host form's results in the stage
-constexpr size_t kHostInts = 12;    // ok model n_matches best_it_H best_it_F n_inliers_H n_inliers_F best_good
-                                    // second_good n_similar status -
-constexpr size_t kHostFloats = 36;  // SH SF RH parallax H21 F21 R21 t21 (34)
 
 }  // namespace
 
@@ -990,14 +964,14 @@ int orbx_initializer_create(orbx_matcher* m, int max_batch, int kcap, int max_it
     s->kcap = kcap;
     s->max_iterations = max_iterations;
     const size_t B = (size_t)max_batch, slots = B * kcap, its = B * max_iterations;
-    const size_t o_pts = 0, o_idx1 = o_pts + up256(slots * 4 * 8), o_norm = o_idx1 + up256(slots * 4),
-                 o_state = o_norm + up256(B * 8 * 8), o_mats = o_state + up256(B * kInitState * 4),
-                 o_bad = o_mats + up256(its * kInitMats * 8), o_scores = o_bad + up256(its * 4),
-                 o_inl = o_scores + up256(its * 2 * 8), o_hyp = o_inl + up256(slots),
-                 o_cosw = o_hyp + up256(B * kInitHyps * 12 * 8), o_good = o_cosw + up256(slots * kInitHyps * 8),
-                 o_par = o_good + up256(B * kInitHyps * 4), total = o_par + up256(B * kInitHyps * 8);
+    Layout L(up256);
+    const size_t o_pts = L.take(slots * 4 * 8), o_idx1 = L.take(slots * 4), o_norm = L.take(B * 8 * 8),
+                 o_state = L.take(B * kInitState * 4), o_mats = L.take(its * kInitMats * 8), o_bad = L.take(its * 4),
+                 o_scores = L.take(its * 2 * 8), o_inl = L.take(slots), o_hyp = L.take(B * kInitHyps * 12 * 8),
+                 o_cosw = L.take(slots * kInitHyps * 8), o_good = L.take(B * kInitHyps * 4),
+                 o_par = L.take(B * kInitHyps * 8);
     hipError_t e = hipSetDevice(s->device);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->work, total);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->work, L.total());
     if (e != hipSuccess) {
         delete s;
         set_last_error(std::string("orbx_initializer_create: ") + hipGetErrorString(e));
@@ -1026,7 +1000,7 @@ void orbx_initializer_destroy(orbx_initializer* s) {
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     if (s->work) (void)hipFree(s->work);
-    if (s->stage) (void)hipFree(s->stage);
+    s->stage.release();
     delete s;
 }
 
@@ -1080,106 +1054,55 @@ int orbx_initializer_initialize(orbx_initializer* s, const orbx_initializer_batc
     if (in->batch != 1) return fail(ORBX_ERR_ARG, "the host form takes one frame pair");
     int rc = check_batch(s, in);
     if (rc) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
+    CallClock clock(s->matcher);
     const size_t kcap = (size_t)in->kcap, its = (size_t)in->max_iterations;
     const int n1 = in->n1[0] < 0 ? 0 : (in->n1[0] > in->kcap ? in->kcap : in->n1[0]);
     const int n2 = in->n2[0] < 0 ? 0 : (in->n2[0] > in->kcap ? in->kcap : in->n2[0]);
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = s->stream;
-    const size_t nkeys = up256(kcap * sizeof(orbx_keypoint)), c1 = up256(kcap), c4 = up256(kcap * 4);
-    const size_t o_n = 0, o_k1 = 256, o_k2 = o_k1 + nkeys, o_m = o_k2 + nkeys, o_sets = o_m + c4,
-                 o_out = o_sets + up256(its * 32);
-    // results: ints, floats, inliers_H, inliers_F, triangulated, p3d
-    const size_t r_fl = kHostInts * 4, r_ih = up256(r_fl + kHostFloats * 4), r_if = r_ih + c1, r_tr = r_if + c1,
-                 r_p3d = r_tr + c1, r_total = r_p3d + up256(kcap * 12);
-    const size_t total = o_out + r_total;
-    if (s->stage_cap < total) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (s->stage) HIP_TRY(hipFree(s->stage));
-        s->stage = nullptr;
-        s->stage_cap = 0;
-        HIP_TRY(hipMalloc((void**)&s->stage, total));
-        s->stage_cap = total;
-    }
-    char* p = s->stage;
-    const int32_t n12[2] = {n1, n2};
-    // pageable sources: staged by the runtime before each call returns
-    HIP_TRY(hipMemcpyAsync(p + o_n, n12, 8, hipMemcpyHostToDevice, st));
-    if (n1 > 0) {
-        HIP_TRY(hipMemcpyAsync(p + o_k1, in->keys1, (size_t)n1 * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(p + o_m, in->matches12, (size_t)n1 * 4, hipMemcpyHostToDevice, st));
-    }
-    if (n2 > 0)
-        HIP_TRY(hipMemcpyAsync(p + o_k2, in->keys2, (size_t)n2 * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(p + o_sets, in->sets, its * 32, hipMemcpyHostToDevice, st));
+    const size_t N1 = (size_t)n1;
+    const struct {
+        int32_t n1, n2;
+    } n12{n1, n2}, *d_n = nullptr;
     orbx_initializer_batch d = *in;
-    d.n1 = (const int32_t*)(p + o_n);
-    d.n2 = (const int32_t*)(p + o_n) + 1;
-    d.keys1 = (const orbx_keypoint*)(p + o_k1);
-    d.keys2 = (const orbx_keypoint*)(p + o_k2);
-    d.matches12 = (const int32_t*)(p + o_m);
-    d.sets = (const int32_t*)(p + o_sets);
-    char* r = p + o_out;
-    int32_t* ints = (int32_t*)r;
-    float* fl = (float*)(r + r_fl);
     orbx_initializer_result o{};
-    o.ok = ints;
-    o.model = ints + 1;
-    o.n_matches = ints + 2;
-    o.best_it_H = ints + 3;
-    o.best_it_F = ints + 4;
-    o.n_inliers_H = ints + 5;
-    o.n_inliers_F = ints + 6;
-    o.best_good = ints + 7;
-    o.second_good = ints + 8;
-    o.n_similar = ints + 9;
-    o.status = ints + 10;
-    o.SH = fl;
-    o.SF = fl + 1;
-    o.RH = fl + 2;
-    o.parallax = fl + 3;
-    o.H21 = fl + 4;
-    o.F21 = fl + 13;
-    o.R21 = fl + 22;
-    o.t21 = fl + 31;
-    o.inliers_H = (uint8_t*)(r + r_ih);
-    o.inliers_F = (uint8_t*)(r + r_if);
-    o.triangulated = (uint8_t*)(r + r_tr);
-    o.p3d = (float*)(r + r_p3d);
+    HostStage h(up256);
+    h.in(&d_n, &n12, 1, 1);
+    h.in(&d.keys1, in->keys1, N1, kcap);
+    h.in(&d.keys2, in->keys2, (size_t)n2, kcap);
+    h.in(&d.matches12, in->matches12, N1, kcap);
+    h.in(&d.sets, in->sets, 8 * its, 8 * its);
+    // results: twelve ints (one spare) and the floats packed, then each array rounded to 256
+    h.out(&o.ok, &out->ok, 1, 1);
+    h.out(&o.model, &out->model, 1, 1);
+    h.out(&o.n_matches, &out->n_matches, 1, 1);
+    h.out(&o.best_it_H, &out->best_it_H, 1, 1);
+    h.out(&o.best_it_F, &out->best_it_F, 1, 1);
+    h.out(&o.n_inliers_H, &out->n_inliers_H, 1, 1);
+    h.out(&o.n_inliers_F, &out->n_inliers_F, 1, 1);
+    h.out(&o.best_good, &out->best_good, 1, 1);
+    h.out(&o.second_good, &out->second_good, 1, 1);
+    h.out(&o.n_similar, &out->n_similar, 1, 1);
+    h.out(&o.status, &out->status, 1, 2);
+    h.out(&o.SH, &out->SH, 1, 1);
+    h.out(&o.SF, &out->SF, 1, 1);
+    h.out(&o.RH, &out->RH, 1, 1);
+    h.out(&o.parallax, &out->parallax, 1, 1);
+    h.out(&o.H21, &out->H21, 9, 9);
+    h.out(&o.F21, &out->F21, 9, 9);
+    h.out(&o.R21, &out->R21, 9, 9);
+    h.out(&o.t21, &out->t21, 3, 3);
+    h.res.align256();
+    h.out(&o.inliers_H, &out->inliers_H, N1, up256(kcap));
+    h.out(&o.inliers_F, &out->inliers_F, N1, up256(kcap));
+    h.out(&o.triangulated, &out->triangulated, N1, up256(kcap));
+    h.out(&o.p3d, &out->p3d, 3 * N1, up256(kcap * 12) / 4);
+    HIP_TRY(h.stage(s->stage, st));
+    d.n1 = &d_n->n1;
+    d.n2 = &d_n->n2;
     rc = orbx_initializer_initialize_device(s, &d, &o, st);
     if (rc) return rc;
-    std::vector<char> h(r_total);
-    HIP_TRY(hipMemcpyAsync(h.data(), r, r_total, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int32_t* hi = (const int32_t*)h.data();
-    const float* hf = (const float*)(h.data() + r_fl);
-    if (out->ok) *out->ok = hi[0];
-    if (out->model) *out->model = hi[1];
-    if (out->n_matches) *out->n_matches = hi[2];
-    if (out->best_it_H) *out->best_it_H = hi[3];
-    if (out->best_it_F) *out->best_it_F = hi[4];
-    if (out->n_inliers_H) *out->n_inliers_H = hi[5];
-    if (out->n_inliers_F) *out->n_inliers_F = hi[6];
-    if (out->best_good) *out->best_good = hi[7];
-    if (out->second_good) *out->second_good = hi[8];
-    if (out->n_similar) *out->n_similar = hi[9];
-    if (out->status) *out->status = hi[10];
-    if (out->SH) *out->SH = hf[0];
-    if (out->SF) *out->SF = hf[1];
-    if (out->RH) *out->RH = hf[2];
-    if (out->parallax) *out->parallax = hf[3];
-    if (out->H21) std::memcpy(out->H21, hf + 4, 36);
-    if (out->F21) std::memcpy(out->F21, hf + 13, 36);
-    if (out->R21) std::memcpy(out->R21, hf + 22, 36);
-    if (out->t21) std::memcpy(out->t21, hf + 31, 12);
-    if (n1 > 0) {
-        if (out->inliers_H) std::memcpy(out->inliers_H, h.data() + r_ih, (size_t)n1);
-        if (out->inliers_F) std::memcpy(out->inliers_F, h.data() + r_if, (size_t)n1);
-        if (out->triangulated) std::memcpy(out->triangulated, h.data() + r_tr, (size_t)n1);
-        if (out->p3d) std::memcpy(out->p3d, h.data() + r_p3d, (size_t)n1 * 12);
-    }
-    matcher_set_last_call_us(s->matcher,
-                             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+    HIP_TRY(h.download(st));
     return ORBX_OK;
 }
 

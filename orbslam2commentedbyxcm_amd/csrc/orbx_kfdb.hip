@@ -28,7 +28,7 @@
 
 #include "orbx.h"
 #include "orbx_block_sort.h"
-#include "orbx_error.h"
+#include "orbx_host.h"
 
 namespace orbx {
 
@@ -382,12 +382,9 @@ struct orbx_kfdb {
     int32_t* count = nullptr;
     float* reloc = nullptr;
     int32_t* meta = nullptr;  // alive, rank, order [max_kf] each, covis [max_kf][10]
-    char* work = nullptr;
-    size_t work_cap = 0;
-    char* stage = nullptr;    // host-form staging
-    size_t stage_cap = 0;
-    char* stage_add = nullptr;  // orbx_kfdb_add's BowVector
-    size_t stage_add_cap = 0;
+    orbx::DeviceBuffer work;
+    orbx::DeviceBuffer stage;      // host-form staging
+    orbx::DeviceBuffer stage_add;  // orbx_kfdb_add's BowVector
     // membership lives on the host (ids are the caller's) and is uploaded before use
     std::vector<int32_t> h_meta;
     std::vector<long long> seq;
@@ -400,22 +397,6 @@ namespace {
 
 using namespace orbx;
 
-int fail(int code, const char* what) {
-    set_last_error(what);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                               \
-    do {                                                                            \
-        hipError_t _e = (expr);                                                     \
-        if (_e != hipSuccess) {                                                     \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));      \
-            return ORBX_ERR_HIP;                                                    \
-        }                                                                           \
-    } while (0)
-
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int32_t* h_alive(orbx_kfdb* d) { return d->h_meta.data(); }
 int32_t* h_rank(orbx_kfdb* d) { return d->h_meta.data() + d->max_kf; }
 int32_t* h_order(orbx_kfdb* d) { return d->h_meta.data() + 2 * (size_t)d->max_kf; }
@@ -427,20 +408,11 @@ KfdbDev view(orbx_kfdb* d) {
 }
 
 void free_db(orbx_kfdb* d) {
-    void* ptrs[] = {d->words, d->values, d->count, d->reloc, d->meta, d->work, d->stage, d->stage_add};
+    void* ptrs[] = {d->words, d->values, d->count, d->reloc, d->meta};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    for (DeviceBuffer* b : {&d->work, &d->stage, &d->stage_add}) b->release();
     if (d->stream) (void)hipStreamDestroy(d->stream);
-}
-
-int reserve(char** buf, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return ORBX_OK;
-    if (*buf) (void)hipFree(*buf);  // synchronises with the work that still reads it
-    *buf = nullptr;
-    *cap = 0;
-    HIP_TRY(hipMalloc((void**)buf, bytes));
-    *cap = bytes;
-    return ORBX_OK;
 }
 
 // One database, one stream at a time: a call on another stream first waits for the last one.
@@ -497,9 +469,8 @@ int detect(orbx_kfdb* d, int loop, int batch, const int32_t* d_qword, const doub
     rc = flush_meta(d, s);
     if (rc) return rc;
     const size_t cells = (size_t)batch * d->max_kf, b_c = up256(cells * 4);
-    rc = reserve(&d->work, &d->work_cap, 6 * b_c + up256((size_t)batch * 4));
-    if (rc) return rc;
-    char* w = d->work;
+    HIP_TRY(d->work.reserve(6 * b_c + up256((size_t)batch * 4), s));
+    char* w = d->work.p;
     int32_t* words = d_words ? d_words : (int32_t*)w;
     int32_t* minword = (int32_t*)(w + b_c);
     float* score = d_score ? d_score : (float*)(w + 2 * b_c);
@@ -564,9 +535,8 @@ int detect_host(orbx_kfdb* d, int loop, const int32_t* word, const double* value
     const size_t b_w = up256((size_t)qcap * 4), b_v = up256((size_t)qcap * 8),
                  b_conn = up256((size_t)(nconnected > 0 ? nconnected : 1) * 4),
                  b_cand = up256((size_t)(max_cand > 0 ? max_cand : 1) * 4);
-    rc = reserve(&d->stage, &d->stage_cap, b_w + b_v + b_conn + b_cand + 256);
-    if (rc) return rc;
-    char* p = d->stage;
+    HIP_TRY(d->stage.reserve(b_w + b_v + b_conn + b_cand + 256, s));
+    char* p = d->stage.p;
     int32_t* d_w = (int32_t*)p;
     double* d_v = (double*)(p + b_w);
     int32_t* d_conn = (int32_t*)(p + b_w + b_v);
@@ -705,10 +675,9 @@ int orbx_kfdb_add_batch_device(orbx_kfdb* d, int n, const int32_t* ids, const in
     for (int i = 0; i < n; i++)
         if (cnt[i] < 0 || cnt[i] > d->cap || cnt[i] > src_cap)
             return fail(ORBX_ERR_CAPACITY, "BowVector longer than the database's cap");
-    rc = reserve(&d->stage, &d->stage_cap, up256((size_t)n * 4));
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(d->stage, ids, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    k_kfdb_add<<<n, 256, 0, s>>>(d->words, d->values, d->count, d->reloc, d->max_kf, d->cap, (const int32_t*)d->stage,
+    HIP_TRY(d->stage.reserve(up256((size_t)n * 4), s));
+    HIP_TRY(hipMemcpyAsync(d->stage.p, ids, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    k_kfdb_add<<<n, 256, 0, s>>>(d->words, d->values, d->count, d->reloc, d->max_kf, d->cap, (const int32_t*)d->stage.p,
                                  d_bow_word, d_bow_value, d_nbow, src_cap);
     HIP_TRY(hipGetLastError());
     for (int i = 0; i < n; i++) {
@@ -729,11 +698,10 @@ int orbx_kfdb_add(orbx_kfdb* d, int id, const int32_t* word, const double* value
     if (rc) return rc;
     const int cap = n > 0 ? n : 1;
     const size_t b_w = up256((size_t)cap * 4), b_v = up256((size_t)cap * 8);
-    rc = reserve(&d->stage_add, &d->stage_add_cap, b_w + b_v + 256);
-    if (rc) return rc;
-    int32_t* d_w = (int32_t*)d->stage_add;
-    double* d_v = (double*)(d->stage_add + b_w);
-    int32_t* d_n = (int32_t*)(d->stage_add + b_w + b_v);
+    HIP_TRY(d->stage_add.reserve(b_w + b_v + 256, s));
+    int32_t* d_w = (int32_t*)d->stage_add.p;
+    double* d_v = (double*)(d->stage_add.p + b_w);
+    int32_t* d_n = (int32_t*)(d->stage_add.p + b_w + b_v);
     if (n) {
         HIP_TRY(hipMemcpyAsync(d_w, word, (size_t)n * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d_v, value, (size_t)n * 8, hipMemcpyHostToDevice, s));

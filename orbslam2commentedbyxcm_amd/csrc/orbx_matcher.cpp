@@ -18,26 +18,12 @@
 #include <vector>
 
 #include "orbx.h"
-#include "orbx_error.h"
+#include "orbx_host.h"
 #include "orbx_kernels.h"
 
 using namespace orbx;
 
 namespace {
-
-int fail(int code, const char* what) {
-    set_last_error(what);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                               \
-    do {                                                                            \
-        hipError_t _e = (expr);                                                     \
-        if (_e != hipSuccess) {                                                     \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));      \
-            return ORBX_ERR_HIP;                                                    \
-        }                                                                           \
-    } while (0)
 
 constexpr int kNumCellsHost = kGridCols * kGridRows;
 constexpr int TH_HIGH = 100;  // ORBmatcher.cc:38
@@ -122,8 +108,6 @@ struct Arena {
         cap = used = dirty = 0;
     }
 };
-
-size_t pad(size_t b) { return ((b + 255) & ~(size_t)255) + 256; }
 
 // Pinned staging for the asynchronous device calls' small host tables: a ring of slots,
 // each reused only once the copy that last read it has run (its event), so a call never
@@ -220,24 +204,15 @@ struct orbx_matcher {
     long long ncalls = 0;
     int footprint = 0;  // orbx_matcher_set_footprint: 0 full, 1 small, 2 split, 3 one wave, 4 lean, 5 lean split
     // device-only scratch of the batched device calls (no pinned mirror)
-    char* dscr = nullptr;
-    size_t dscr_cap = 0;
+    DeviceBuffer dscr;
     // tables of orbx_search_for_triangulation_batch_device (device-only)
-    char* tscr = nullptr;
-    size_t tscr_cap = 0;
+    DeviceBuffer tscr;
     // queries, problems and grids of orbx_search_local_points_device (device-only)
-    char* lscr = nullptr;
-    size_t lscr_cap = 0;
+    DeviceBuffer lscr;
     // edge records of orbx_pose_optimization_batch_device, and the single call's frame (device-only)
-    char* pscr = nullptr;
-    size_t pscr_cap = 0;
-    char* pstage = nullptr;
-    size_t pstage_cap = 0;
+    DeviceBuffer pscr, pstage;
     // tables of orbx_triangulate_pairs_batch_device, and the single call's keyframes and results (device-only)
-    char* gscr = nullptr;
-    size_t gscr_cap = 0;
-    char* gstage = nullptr;
-    size_t gstage_cap = 0;
+    DeviceBuffer gscr, gstage;
     StageRing stage;
     // wall time of the newest drop-in host call (entry to return), as a C++ caller sees it
     double last_call_us = 0.0;
@@ -254,18 +229,6 @@ int matcher_device(const orbx_matcher* m) { return m->device; }
 hipStream_t matcher_stream(const orbx_matcher* m) { return m->stream; }
 void matcher_set_last_call_us(orbx_matcher* m, double us) { m->last_call_us = us; }
 }  // namespace orbx
-
-namespace {
-// Scoped: stores the enclosing host call's wall time in m->last_call_us.
-struct CallClock {
-    orbx_matcher* m;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    explicit CallClock(orbx_matcher* mm) : m(mm) {}
-    ~CallClock() {
-        if (m) m->last_call_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    }
-};
-}  // namespace
 
 namespace {
 
@@ -449,13 +412,7 @@ void orbx_matcher_destroy(orbx_matcher* m) {
     (void)hipSetDevice(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
     m->arena.release();
-    if (m->dscr) (void)hipFree(m->dscr);
-    if (m->tscr) (void)hipFree(m->tscr);
-    if (m->lscr) (void)hipFree(m->lscr);
-    if (m->pscr) (void)hipFree(m->pscr);
-    if (m->pstage) (void)hipFree(m->pstage);
-    if (m->gscr) (void)hipFree(m->gscr);
-    if (m->gstage) (void)hipFree(m->gstage);
+    for (DeviceBuffer* b : {&m->dscr, &m->tscr, &m->lscr, &m->pscr, &m->pstage, &m->gscr, &m->gstage}) b->release();
     m->stage.release();
     if (m->hmp) (void)hipHostFree(m->hmp);
     for (auto& slot : m->ev)
@@ -962,30 +919,19 @@ int orbx_search_local_points_device(orbx_matcher* m, const orbx_mappoints_device
     const bool split = m->footprint == 2;
     const bool grids = split || m->footprint == 5;
     const size_t nt = (size_t)(total > 0 ? total : 1);
-    const size_t need = pad(sizeof(ProjQuery) * nt) + pad(nt * 32) + pad(sizeof(ProjProblem) * B) +
-                        pad(sizeof(long long) * B) + pad(sizeof(unsigned long long) * kProjScratchWords * nt) +
-                        pad(sizeof(int32_t) * (B + 1)) + (grids ? pad(seq_grid_bytes(cap, nlevels) * B) : 0);
-    if (m->lscr_cap < need) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (m->lscr) HIP_TRY(hipFree(m->lscr));
-        m->lscr = nullptr;
-        m->lscr_cap = 0;
-        HIP_TRY(hipMalloc((void**)&m->lscr, need));
-        m->lscr_cap = need;
-    }
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        char* p = m->lscr + o;
-        o += pad(bytes);
-        return p;
-    };
-    auto* d_q = (ProjQuery*)take(sizeof(ProjQuery) * nt);
-    auto* d_qd = (uint8_t*)take(nt * 32);
-    auto* d_prob = (ProjProblem*)take(sizeof(ProjProblem) * B);
-    auto* d_off = (long long*)take(sizeof(long long) * B);
-    auto* d_scr = (unsigned long long*)take(sizeof(unsigned long long) * kProjScratchWords * nt);
-    auto* d_loff = (int32_t*)take(sizeof(int32_t) * (B + 1));
-    auto* d_grids = grids ? (unsigned char*)take(seq_grid_bytes(cap, nlevels) * B) : nullptr;
+    Layout L(pad);
+    const size_t o_q = L.take(sizeof(ProjQuery) * nt), o_qd = L.take(nt * 32), o_prob = L.take(sizeof(ProjProblem) * B),
+                 o_off = L.take(sizeof(long long) * B), o_scr = L.take(sizeof(unsigned long long) * kProjScratchWords * nt),
+                 o_loff = L.take(sizeof(int32_t) * (B + 1)), o_grids = grids ? L.take(seq_grid_bytes(cap, nlevels) * B) : 0;
+    HIP_TRY(m->lscr.reserve(L.total(), s));
+    char* p = m->lscr.p;
+    auto* d_q = (ProjQuery*)(p + o_q);
+    auto* d_qd = (uint8_t*)(p + o_qd);
+    auto* d_prob = (ProjProblem*)(p + o_prob);
+    auto* d_off = (long long*)(p + o_off);
+    auto* d_scr = (unsigned long long*)(p + o_scr);
+    auto* d_loff = (int32_t*)(p + o_loff);
+    auto* d_grids = grids ? (unsigned char*)(p + o_grids) : nullptr;
     char* h = nullptr;
     int slot = 0;
     HIP_TRY(m->stage.get(sizeof(int32_t) * (B + 1), &h, &slot));
@@ -1235,55 +1181,40 @@ int orbx_search_for_triangulation_batch_device(orbx_matcher* m, int nkf, const o
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = stream ? (hipStream_t)stream : m->stream;
     const size_t P = (size_t)npairs;
-    const size_t need = pad(sizeof(TriKF) * (size_t)nkf) + pad(sizeof(TriPair) * P) + 2 * pad(sizeof(float) * 32) +
-                        pad(sizeof(TriQuery) * P * cap) + pad(sizeof(TriProblem) * P) +
-                        pad(sizeof(unsigned long long) * P * cap);
-    if (m->tscr_cap < need) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (m->tscr) HIP_TRY(hipFree(m->tscr));
-        m->tscr = nullptr;
-        m->tscr_cap = 0;
-        HIP_TRY(hipMalloc((void**)&m->tscr, need));
-        m->tscr_cap = need;
-    }
     // tables first (one staged copy), then the device-only work areas
-    const size_t tab = pad(sizeof(TriKF) * (size_t)nkf) + pad(sizeof(TriPair) * P) + 2 * pad(sizeof(float) * 32);
-    char* q = m->tscr;
-    auto take = [&q](size_t bytes) {
-        char* r = q;
-        q += pad(bytes);
-        return r;
-    };
+    Layout L(pad);
+    const size_t o_kf = L.take(sizeof(TriKF) * (size_t)nkf), o_tp = L.take(sizeof(TriPair) * P),
+                 o_sc = L.take(sizeof(float) * 32), o_sg = L.take(sizeof(float) * 32), tab = L.total(),
+                 o_q = L.take(sizeof(TriQuery) * P * cap), o_probs = L.take(sizeof(TriProblem) * P),
+                 o_scr = L.take(sizeof(unsigned long long) * P * cap);
+    HIP_TRY(m->tscr.reserve(L.total(), s));
+    char* p = m->tscr.p;
     TriBatch tb{};
-    auto* d_kf = (TriKF*)take(sizeof(TriKF) * (size_t)nkf);
-    auto* d_tp = (TriPair*)take(sizeof(TriPair) * P);
-    auto* d_sc = (float*)take(sizeof(float) * 32);
-    auto* d_sg = (float*)take(sizeof(float) * 32);
-    tb.q = (TriQuery*)take(sizeof(TriQuery) * P * cap);
-    tb.probs = (TriProblem*)take(sizeof(TriProblem) * P);
-    auto* d_scr = (unsigned long long*)take(sizeof(unsigned long long) * P * cap);
+    tb.q = (TriQuery*)(p + o_q);
+    tb.probs = (TriProblem*)(p + o_probs);
+    auto* d_scr = (unsigned long long*)(p + o_scr);
     char* h = nullptr;
     int slot = 0;
     HIP_TRY(m->stage.get(tab, &h, &slot));
     std::memset(h, 0, tab);
-    std::memcpy(h + ((char*)d_kf - m->tscr), tk.data(), sizeof(TriKF) * (size_t)nkf);
-    std::memcpy(h + ((char*)d_tp - m->tscr), tp.data(), sizeof(TriPair) * P);
-    float* hs = (float*)(h + ((char*)d_sc - m->tscr));
-    float* hg = (float*)(h + ((char*)d_sg - m->tscr));
+    std::memcpy(h + o_kf, tk.data(), sizeof(TriKF) * (size_t)nkf);
+    std::memcpy(h + o_tp, tp.data(), sizeof(TriPair) * P);
+    float* hs = (float*)(h + o_sc);
+    float* hg = (float*)(h + o_sg);
     for (int l = 0; l < cam->nlevels; l++) {
         hs[l] = cam->scale_factors[l];
         hg[l] = cam->level_sigma2[l];
     }
-    HIP_TRY(hipMemcpyAsync(m->tscr, h, tab, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(p, h, tab, hipMemcpyHostToDevice, s));
     HIP_TRY(m->stage.copied(slot, s));
-    tb.kfs = d_kf;
-    tb.pairs = d_tp;
+    tb.kfs = (const TriKF*)(p + o_kf);
+    tb.pairs = (const TriPair*)(p + o_tp);
     tb.npairs = npairs;
     tb.cap = cap;
     tb.only_stereo = only_stereo ? 1 : 0;
     tb.check_ori = m->check_ori;
-    tb.scale2 = d_sc;
-    tb.sigma2_2 = d_sg;
+    tb.scale2 = (const float*)(p + o_sc);
+    tb.sigma2_2 = (const float*)(p + o_sg);
     tb.matches12 = d_matches12;
     tb.pairs_out = d_pairs;
     tb.npairs_out = d_npairs;
@@ -1906,9 +1837,18 @@ void stereo_level0(StereoBatch& sb, const PyrView& vl, const PyrView& vr, int le
 // words of the per-pair (octave, row) offsets + row coverage counts (StereoBatch::row_off)
 size_t stereo_off_words(const StereoBatch& sb) { return (size_t)sb.nlevels * sb.rows + 1 + sb.rows; }
 
-size_t stereo_scratch(const StereoBatch& sb, int batch) {
-    return pad(sizeof(int32_t) * (size_t)batch * stereo_off_words(sb)) +
-           pad(sizeof(int32_t) * (size_t)batch * sb.band_cap) + pad(sizeof(StereoResult) * (size_t)batch * sb.cap);
+// the device-only work areas of `batch` pairs: offsets in one buffer, and its size
+struct StereoScratch {
+    size_t row_off, row_idx, res, total;
+};
+StereoScratch stereo_scratch(const StereoBatch& sb, int batch) {
+    Layout L(pad);
+    StereoScratch r{};
+    r.row_off = L.take(sizeof(int32_t) * (size_t)batch * stereo_off_words(sb));
+    r.row_idx = L.take(sizeof(int32_t) * (size_t)batch * sb.band_cap);
+    r.res = L.take(sizeof(StereoResult) * (size_t)batch * sb.cap);
+    r.total = L.total();
+    return r;
 }
 
 }  // namespace
@@ -1948,7 +1888,7 @@ int orbx_compute_stereo_matches(orbx_matcher* m, orbx_extractor* ex_left, int le
     sb.max_d = max_disparity;
     HIP_TRY(hipSetDevice(m->device));
     const size_t need = pad(sizeof(orbx_keypoint) * sb.cap) * 2 + pad((size_t)sb.cap * 32) * 2 + 2 * pad(sizeof(int32_t)) +
-                        2 * pad(sizeof(float) * sb.cap) + stereo_scratch(sb, 1);
+                        2 * pad(sizeof(float) * sb.cap) + stereo_scratch(sb, 1).total;
     HIP_TRY(m->arena.reserve(need));
     m->arena.used = 0;
     auto* d_kl = m->arena.take<orbx_keypoint>(sb.cap);
@@ -2011,21 +1951,11 @@ int orbx_compute_stereo_matches_batch_device(orbx_matcher* m, orbx_extractor* ex
         return fail(ORBX_ERR_ARG, "pair range outside the extractors' last batches");
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = stream ? (hipStream_t)stream : m->stream;
-    const size_t need = stereo_scratch(sb, batch);
-    if (m->dscr_cap < need) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (m->dscr) HIP_TRY(hipFree(m->dscr));
-        m->dscr = nullptr;
-        m->dscr_cap = 0;
-        HIP_TRY(hipMalloc((void**)&m->dscr, need));
-        m->dscr_cap = need;
-    }
-    char* p = m->dscr;
-    sb.row_off = (int32_t*)p;
-    p += pad(sizeof(int32_t) * (size_t)batch * stereo_off_words(sb));
-    sb.row_idx = (int32_t*)p;
-    p += pad(sizeof(int32_t) * (size_t)batch * sb.band_cap);
-    sb.res = (StereoResult*)p;
+    const StereoScratch scr = stereo_scratch(sb, batch);
+    HIP_TRY(m->dscr.reserve(scr.total, s));
+    sb.row_off = (int32_t*)(m->dscr.p + scr.row_off);
+    sb.row_idx = (int32_t*)(m->dscr.p + scr.row_idx);
+    sb.res = (StereoResult*)(m->dscr.p + scr.res);
     sb.keys_l = d_kps_l;
     sb.desc_l = d_desc_l;
     sb.n_l = d_n_l;
@@ -2067,15 +1997,7 @@ int orbx_pose_optimization_batch_device(orbx_matcher* m, const orbx_pose_optimiz
     if ((size_t)B * (size_t)cap >= ((size_t)1 << 31)) return fail(ORBX_ERR_ARG, "batch x cap of 2^31 or more");
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = stream ? (hipStream_t)stream : m->stream;
-    const size_t need = pose_opt_workspace_bytes(B, cap);
-    if (m->pscr_cap < need) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (m->pscr) HIP_TRY(hipFree(m->pscr));
-        m->pscr = nullptr;
-        m->pscr_cap = 0;
-        HIP_TRY(hipMalloc((void**)&m->pscr, need));
-        m->pscr_cap = need;
-    }
+    HIP_TRY(m->pscr.reserve(pose_opt_workspace_bytes(B, cap), s));
     PoseOptArgs A{};
     A.kps = po->kps;
     A.n = po->n;
@@ -2102,7 +2024,7 @@ int orbx_pose_optimization_batch_device(orbx_matcher* m, const orbx_pose_optimiz
     A.discard_outliers = po->discard_outliers;
     A.mp_obs = po->mp_obs;
     A.nmatches_map = po->nmatches_map;
-    HIP_TRY(launch_pose_opt(A, B, m->pscr, s));
+    HIP_TRY(launch_pose_opt(A, B, m->pscr.p, s));
     return ORBX_OK;
 }
 
@@ -2117,42 +2039,30 @@ int orbx_pose_optimization(orbx_matcher* m, const orbx_keypoint* keys, int n, co
     CallClock clock(m);
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = m->stream;
-    const int cap = n > 0 ? n : 1;
-    const size_t nt = (size_t)(n_mp > 0 ? n_mp : 1);
-    // inputs, then the outputs as one block: Tcw_opt [12], ninliers, ninit, trace [8], outlier [cap]
-    const size_t o_keys = 0, o_ur = o_keys + pad(sizeof(orbx_keypoint) * cap), o_mp = o_ur + pad(4 * (size_t)cap),
-                 o_pos = o_mp + pad(4 * (size_t)cap), o_in = o_pos + pad(12 * nt), o_out = o_in + pad(64),
-                 out_bytes = 12 * 4 + 2 * 4 + 8 * 4 + (size_t)cap, total = o_out + pad(out_bytes);
-    if (m->pstage_cap < total) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (m->pstage) HIP_TRY(hipFree(m->pstage));
-        m->pstage = nullptr;
-        m->pstage_cap = 0;
-        HIP_TRY(hipMalloc((void**)&m->pstage, total));
-        m->pstage_cap = total;
-    }
-    char* p = m->pstage;
-    // pageable sources: staged by the runtime before each call returns
-    if (n > 0) {
-        HIP_TRY(hipMemcpyAsync(p + o_keys, keys, sizeof(orbx_keypoint) * n, hipMemcpyHostToDevice, s));
-        if (u_right) HIP_TRY(hipMemcpyAsync(p + o_ur, u_right, 4 * (size_t)n, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(p + o_mp, frame_mp, 4 * (size_t)n, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(p + o_out + 88, outlier, (size_t)n, hipMemcpyHostToDevice, s));
-    }
-    if (n_mp > 0) HIP_TRY(hipMemcpyAsync(p + o_pos, mp_pos, 12 * (size_t)n_mp, hipMemcpyHostToDevice, s));
-    int32_t in[16] = {};
-    std::memcpy(in, Tcw, 48);
-    in[12] = n;
-    HIP_TRY(hipMemcpyAsync(p + o_in, in, sizeof(in), hipMemcpyHostToDevice, s));
+    const size_t cap = (size_t)(n > 0 ? n : 1), N = (size_t)n;
+    struct {
+        float Tcw[12];
+        int32_t n, spare[3];
+    } in{}, *d_in = nullptr;
+    std::memcpy(in.Tcw, Tcw, sizeof(in.Tcw));
+    in.n = n;
     orbx_pose_optimization_batch po{};
+    HostStage st(pad);
+    st.out(&po.Tcw_opt, &Tcw_opt, 12, 12);
+    st.out(&po.ninliers, &ninliers, 1, 1);
+    st.out(&po.ninit, &ninit, 1, 1);
+    st.out(&po.trace, &trace, 8, 8);
+    st.in(&po.kps, keys, N, cap);
+    st.in_optional(&po.u_right, u_right, N, cap);
+    st.in(&po.frame_mp, frame_mp, N, cap);
+    st.inout(&po.outlier, &outlier, N, cap);
+    st.in(&po.mp_pos, mp_pos, 3 * (size_t)n_mp, 3 * (size_t)(n_mp > 0 ? n_mp : 1));
+    st.in(&d_in, &in, 1, 1);
+    HIP_TRY(st.stage(m->pstage, s));
     po.batch = 1;
-    po.kps = (const orbx_keypoint*)(p + o_keys);
-    po.n = (const int32_t*)(p + o_in) + 12;
-    po.cap = cap;
-    po.u_right = u_right ? (const float*)(p + o_ur) : nullptr;
-    po.frame_mp = (int32_t*)(p + o_mp);
+    po.n = &d_in->n;
+    po.cap = (int)cap;
     po.n_mp = n_mp;
-    po.mp_pos = (const float*)(p + o_pos);
     po.inv_level_sigma2 = inv_level_sigma2;
     po.nlevels = nlevels;
     po.fx = fx;
@@ -2160,24 +2070,10 @@ int orbx_pose_optimization(orbx_matcher* m, const orbx_keypoint* keys, int n, co
     po.cx = cx;
     po.cy = cy;
     po.bf = bf;
-    po.Tcw = (const float*)(p + o_in);
-    po.Tcw_opt = (float*)(p + o_out);
-    po.ninliers = (int32_t*)(p + o_out + 48);
-    po.ninit = (int32_t*)(p + o_out + 52);
-    po.trace = (int32_t*)(p + o_out + 56);
-    po.outlier = (uint8_t*)(p + o_out + 88);
+    po.Tcw = d_in->Tcw;
     const int rc = orbx_pose_optimization_batch_device(m, &po, s);
     if (rc) return rc;
-    std::vector<char> h(out_bytes);
-    HIP_TRY(hipMemcpyAsync(h.data(), p + o_out, out_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    std::memcpy(Tcw_opt, h.data(), 48);
-    int32_t counts[2];
-    std::memcpy(counts, h.data() + 48, 8);
-    *ninliers = counts[0];
-    if (ninit) *ninit = counts[1];
-    if (trace) std::memcpy(trace, h.data() + 56, 32);
-    if (n > 0) std::memcpy(outlier, h.data() + 88, (size_t)n);
+    HIP_TRY(st.download(s));
     return ORBX_OK;
 }
 
@@ -2206,15 +2102,7 @@ int orbx_optimize_sim3_batch_device(orbx_matcher* m, const orbx_optimize_sim3_ba
     if (B == 0) return ORBX_OK;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = stream ? (hipStream_t)stream : m->stream;
-    const size_t need = opt_sim3_workspace_bytes(B, os->cap1);
-    if (m->pscr_cap < need) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (m->pscr) HIP_TRY(hipFree(m->pscr));
-        m->pscr = nullptr;
-        m->pscr_cap = 0;
-        HIP_TRY(hipMalloc((void**)&m->pscr, need));
-        m->pscr_cap = need;
-    }
+    HIP_TRY(m->pscr.reserve(opt_sim3_workspace_bytes(B, os->cap1), s));
     OptSim3Args A{};
     A.cap1 = os->cap1;
     A.cap2 = os->cap2;
@@ -2251,7 +2139,7 @@ int orbx_optimize_sim3_batch_device(orbx_matcher* m, const orbx_optimize_sim3_ba
     A.ncorr = os->ncorr;
     A.nbad = os->nbad;
     A.trace = os->trace;
-    HIP_TRY(launch_opt_sim3(A, B, m->pscr, s));
+    HIP_TRY(launch_opt_sim3(A, B, m->pscr.p, s));
     return ORBX_OK;
 }
 
@@ -2266,79 +2154,46 @@ int orbx_optimize_sim3(orbx_matcher* m, const orbx_optimize_sim3_batch* os) {
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = m->stream;
     const size_t c1 = (size_t)(n1 > 0 ? n1 : 1), c2 = (size_t)(n2 > 0 ? n2 : 1);
-    const size_t nt = (size_t)(os->n_mp > 0 ? os->n_mp : 1);
-    // inputs: kps1, mp1, idx2, kps2, mp_pos, one block {Tcw1, Tcw2, R12, t12, s12, n1, n2}; then
-    // the outputs as one block: R12_opt [9], t12_opt [3], s12_opt, ninliers, ncorr, nbad,
-    // trace [4], matches12 [c1]
-    const size_t o_k1 = 0, o_mp1 = o_k1 + pad(sizeof(orbx_keypoint) * c1), o_i2 = o_mp1 + pad(4 * c1),
-                 o_k2 = o_i2 + pad(4 * c1), o_pos = o_k2 + pad(sizeof(orbx_keypoint) * c2), o_in = o_pos + pad(12 * nt),
-                 o_out = o_in + pad(40 * 4), out_bytes = 20 * 4 + 4 * c1, total = o_out + pad(out_bytes);
-    if (m->pstage_cap < total) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (m->pstage) HIP_TRY(hipFree(m->pstage));
-        m->pstage = nullptr;
-        m->pstage_cap = 0;
-        HIP_TRY(hipMalloc((void**)&m->pstage, total));
-        m->pstage_cap = total;
-    }
-    char* p = m->pstage;
-    if (n1 > 0) {
-        HIP_TRY(hipMemcpyAsync(p + o_k1, os->kps1, sizeof(orbx_keypoint) * n1, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(p + o_mp1, os->mp1, 4 * (size_t)n1, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(p + o_i2, os->idx2, 4 * (size_t)n1, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(p + o_out + 80, os->matches12, 4 * (size_t)n1, hipMemcpyHostToDevice, s));
-    }
-    if (n2 > 0) HIP_TRY(hipMemcpyAsync(p + o_k2, os->kps2, sizeof(orbx_keypoint) * n2, hipMemcpyHostToDevice, s));
-    if (os->n_mp > 0) HIP_TRY(hipMemcpyAsync(p + o_pos, os->mp_pos, 12 * (size_t)os->n_mp, hipMemcpyHostToDevice, s));
-    int32_t in[40] = {};
-    std::memcpy(in, os->Tcw1, 48);
-    std::memcpy(in + 12, os->Tcw2, 48);
-    std::memcpy(in + 24, os->R12, 36);
-    std::memcpy(in + 33, os->t12, 12);
-    std::memcpy(in + 36, os->s12, 4);
-    in[37] = n1;
-    in[38] = n2;
-    HIP_TRY(hipMemcpyAsync(p + o_in, in, sizeof(in), hipMemcpyHostToDevice, s));
+    struct {
+        float Tcw1[12], Tcw2[12], R12[9], t12[3], s12;
+        int32_t n1, n2, spare;
+    } in{}, *d_in = nullptr;
+    std::memcpy(in.Tcw1, os->Tcw1, sizeof(in.Tcw1));
+    std::memcpy(in.Tcw2, os->Tcw2, sizeof(in.Tcw2));
+    std::memcpy(in.R12, os->R12, sizeof(in.R12));
+    std::memcpy(in.t12, os->t12, sizeof(in.t12));
+    in.s12 = *os->s12;
+    in.n1 = n1;
+    in.n2 = n2;
     orbx_optimize_sim3_batch d = *os;
+    HostStage st(pad);
+    st.out(&d.R12_opt, &os->R12_opt, 9, 9);
+    st.out(&d.t12_opt, &os->t12_opt, 3, 3);
+    st.out(&d.s12_opt, &os->s12_opt, 1, 1);
+    st.out(&d.ninliers, &os->ninliers, 1, 1);
+    st.out(&d.ncorr, &os->ncorr, 1, 1);
+    st.out(&d.nbad, &os->nbad, 1, 1);
+    st.out(&d.trace, &os->trace, 4, 4);
+    st.in(&d.kps1, os->kps1, (size_t)n1, c1);
+    st.in(&d.mp1, os->mp1, (size_t)n1, c1);
+    st.in(&d.idx2, os->idx2, (size_t)n1, c1);
+    st.inout(&d.matches12, &os->matches12, (size_t)n1, c1);
+    st.in(&d.kps2, os->kps2, (size_t)n2, c2);
+    st.in(&d.mp_pos, os->mp_pos, 3 * (size_t)os->n_mp, 3 * (size_t)(os->n_mp > 0 ? os->n_mp : 1));
+    st.in(&d_in, &in, 1, 1);
+    HIP_TRY(st.stage(m->pstage, s));
     d.cap1 = (int)c1;
     d.cap2 = (int)c2;
-    d.kps1 = (const orbx_keypoint*)(p + o_k1);
-    d.mp1 = (const int32_t*)(p + o_mp1);
-    d.idx2 = (const int32_t*)(p + o_i2);
-    d.kps2 = (const orbx_keypoint*)(p + o_k2);
-    d.mp_pos = (const float*)(p + o_pos);
-    const float* fin = (const float*)(p + o_in);
-    d.Tcw1 = fin;
-    d.Tcw2 = fin + 12;
-    d.R12 = fin + 24;
-    d.t12 = fin + 33;
-    d.s12 = fin + 36;
-    d.n1 = (const int32_t*)(p + o_in) + 37;
-    d.n2 = (const int32_t*)(p + o_in) + 38;
-    float* fout = (float*)(p + o_out);
-    d.R12_opt = fout;
-    d.t12_opt = fout + 9;
-    d.s12_opt = fout + 12;
-    d.ninliers = (int32_t*)(p + o_out) + 13;
-    d.ncorr = (int32_t*)(p + o_out) + 14;
-    d.nbad = (int32_t*)(p + o_out) + 15;
-    d.trace = (int32_t*)(p + o_out) + 16;
-    d.matches12 = (int32_t*)(p + o_out) + 20;
+    d.Tcw1 = d_in->Tcw1;
+    d.Tcw2 = d_in->Tcw2;
+    d.R12 = d_in->R12;
+    d.t12 = d_in->t12;
+    d.s12 = &d_in->s12;
+    d.n1 = &d_in->n1;
+    d.n2 = &d_in->n2;
     const int rc = orbx_optimize_sim3_batch_device(m, &d, s);
     if (rc) return rc;
-    std::vector<char> h(out_bytes);
-    HIP_TRY(hipMemcpyAsync(h.data(), p + o_out, out_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    std::memcpy(os->R12_opt, h.data(), 36);
-    std::memcpy(os->t12_opt, h.data() + 36, 12);
-    std::memcpy(os->s12_opt, h.data() + 48, 4);
-    int32_t c[7];
-    std::memcpy(c, h.data() + 52, 28);
-    if (os->ninliers) *os->ninliers = c[0];
-    if (os->ncorr) *os->ncorr = c[1];
-    if (os->nbad) *os->nbad = c[2];
-    if (os->trace) std::memcpy(os->trace, c + 3, 16);
-    if (n1 > 0) std::memcpy(os->matches12, h.data() + 80, 4 * (size_t)n1);
+    HIP_TRY(st.download(s));
     return ORBX_OK;
 }
 
@@ -2377,21 +2232,16 @@ static int triangulate_launch(orbx_matcher* m, int nkf, const orbx_keyframe_geom
                               const int32_t* d_npairs, float mb, float mbf, const orbx_new_mappoints* out,
                               hipStream_t s) {
     const size_t P = (size_t)npairs;
-    const size_t tab = pad(sizeof(TriGeomKF) * (size_t)nkf) + pad(8 * P) + 2 * pad(sizeof(float) * ORBX_MAX_LEVELS);
-    if (m->gscr_cap < tab) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (m->gscr) HIP_TRY(hipFree(m->gscr));
-        m->gscr = nullptr;
-        m->gscr_cap = 0;
-        HIP_TRY(hipMalloc((void**)&m->gscr, tab));
-        m->gscr_cap = tab;
-    }
+    Layout L(pad);
+    const size_t o_kf = L.take(sizeof(TriGeomKF) * (size_t)nkf), o_pk = L.take(8 * P),
+                 o_sc = L.take(sizeof(float) * ORBX_MAX_LEVELS), o_sg = L.take(sizeof(float) * ORBX_MAX_LEVELS),
+                 tab = L.total();
+    HIP_TRY(m->gscr.reserve(tab, s));
+    char* g = m->gscr.p;
     char* h = nullptr;
     int slot = 0;
     HIP_TRY(m->stage.get(tab, &h, &slot));
     std::memset(h, 0, tab);
-    const size_t o_kf = 0, o_pk = o_kf + pad(sizeof(TriGeomKF) * (size_t)nkf), o_sc = o_pk + pad(8 * P),
-                 o_sg = o_sc + pad(sizeof(float) * ORBX_MAX_LEVELS);
     auto* hk = (TriGeomKF*)(h + o_kf);
     for (int k = 0; k < nkf; k++) hk[k] = geom_record(kfs[k]);
     std::memcpy(h + o_pk, pairs, 8 * P);
@@ -2399,11 +2249,11 @@ static int triangulate_launch(orbx_matcher* m, int nkf, const orbx_keyframe_geom
         ((float*)(h + o_sc))[l] = cam->scale_factors[l];
         ((float*)(h + o_sg))[l] = cam->level_sigma2[l];
     }
-    HIP_TRY(hipMemcpyAsync(m->gscr, h, tab, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(g, h, tab, hipMemcpyHostToDevice, s));
     HIP_TRY(m->stage.copied(slot, s));
     TriGeomArgs A{};
-    A.kfs = (const TriGeomKF*)(m->gscr + o_kf);
-    A.pair_kf = (const int32_t*)(m->gscr + o_pk);
+    A.kfs = (const TriGeomKF*)(g + o_kf);
+    A.pair_kf = (const int32_t*)(g + o_pk);
     A.pairs = d_pairs;
     A.npairs = d_npairs;
     A.cap = cap;
@@ -2416,8 +2266,8 @@ static int triangulate_launch(orbx_matcher* m, int nkf, const orbx_keyframe_geom
     A.mbf = mbf;
     A.nlevels = cam->nlevels;
     A.scale_factor = cam->nlevels > 1 ? cam->scale_factors[1] : 1.0f;  // mfScaleFactor
-    A.scale = (const float*)(m->gscr + o_sc);
-    A.sigma2 = (const float*)(m->gscr + o_sg);
+    A.scale = (const float*)(g + o_sc);
+    A.sigma2 = (const float*)(g + o_sg);
     A.reason = out->reason;
     A.method = out->method;
     A.pos = out->pos;
@@ -2465,70 +2315,43 @@ int orbx_triangulate_pairs(orbx_matcher* m, const orbx_keyframe_geom_device* kf1
     CallClock clock(m);
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = m->stream;
-    const int kcap = std::max(1, std::max(n[0], n[1]));
-    // per keyframe: keys_un, keys, u_right, depth (kcap slots each); then the matched pairs,
-    // {n1, n2, nmatched}; then the outputs as one block: nnew, new_idx, max, min, pos, normal,
-    // reason, method
-    const size_t kb = pad(sizeof(orbx_keypoint) * (size_t)kcap), fb = pad(4 * (size_t)kcap);
-    const size_t per_kf = 2 * kb + 2 * fb;
-    const size_t o_pairs = 2 * per_kf, o_cnt = o_pairs + pad(8 * (size_t)c), o_out = o_cnt + pad(16);
-    const size_t C = (size_t)c;
-    const size_t q_new = 0, q_idx = 16, q_max = q_idx + 4 * C, q_min = q_max + 4 * C, q_pos = q_min + 4 * C,
-                 q_nrm = q_pos + 12 * C, q_rsn = q_nrm + 12 * C, q_mth = q_rsn + C, out_bytes = q_mth + C;
-    const size_t total = o_out + pad(out_bytes);
-    if (m->gstage_cap < total) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (m->gstage) HIP_TRY(hipFree(m->gstage));
-        m->gstage = nullptr;
-        m->gstage_cap = 0;
-        HIP_TRY(hipMalloc((void**)&m->gstage, total));
-        m->gstage_cap = total;
-    }
-    char* p = m->gstage;
-    orbx_keyframe_geom_device d[2];
+    const size_t kcap = (size_t)std::max(1, std::max(n[0], n[1])), C = (size_t)c, nm = (size_t)nmatched;
+    // per keyframe: keys_un, keys, u_right, depth (kcap slots each); then the matched pairs and
+    // the counts; the results are zeroed before the launch
+    const struct {
+        int32_t n[2], nmatched, spare;
+    } cnt{{n[0], n[1]}, nmatched, 0}, *d_cnt = nullptr;
+    orbx_keyframe_geom_device d[2] = {two[0], two[1]};
+    const int32_t* d_matched = nullptr;
+    orbx_new_mappoints dout{};
+    HostStage st(pad);
     for (int k = 0; k < 2; k++) {
-        char* b = p + per_kf * k;
-        const orbx_keyframe_geom_device& K = two[k];
-        d[k] = K;
         const size_t nk = (size_t)n[k];
-        d[k].keys_un = (const orbx_keypoint*)b;
-        d[k].keys = K.keys ? (const orbx_keypoint*)(b + kb) : nullptr;
-        d[k].u_right = K.u_right ? (const float*)(b + 2 * kb) : nullptr;
-        d[k].depth = K.depth ? (const float*)(b + 2 * kb + fb) : nullptr;
-        d[k].n = (const int32_t*)(p + o_cnt) + k;
-        if (nk) {
-            HIP_TRY(hipMemcpyAsync(b, K.keys_un, sizeof(orbx_keypoint) * nk, hipMemcpyHostToDevice, s));
-            if (K.keys) HIP_TRY(hipMemcpyAsync(b + kb, K.keys, sizeof(orbx_keypoint) * nk, hipMemcpyHostToDevice, s));
-            if (K.u_right) HIP_TRY(hipMemcpyAsync(b + 2 * kb, K.u_right, 4 * nk, hipMemcpyHostToDevice, s));
-            if (K.depth) HIP_TRY(hipMemcpyAsync(b + 2 * kb + fb, K.depth, 4 * nk, hipMemcpyHostToDevice, s));
-        }
+        st.in(&d[k].keys_un, two[k].keys_un, nk, kcap);
+        st.in_optional(&d[k].keys, two[k].keys, nk, kcap);
+        st.in_optional(&d[k].u_right, two[k].u_right, nk, kcap);
+        st.in_optional(&d[k].depth, two[k].depth, nk, kcap);
     }
-    if (nmatched > 0) HIP_TRY(hipMemcpyAsync(p + o_pairs, matched, 8 * (size_t)nmatched, hipMemcpyHostToDevice, s));
-    const int32_t cnt[4] = {n[0], n[1], nmatched, 0};
-    HIP_TRY(hipMemcpyAsync(p + o_cnt, cnt, sizeof(cnt), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(p + o_out, 0, out_bytes, s));
-    char* o = p + o_out;
-    const orbx_new_mappoints dout{(uint8_t*)(o + q_rsn), (uint8_t*)(o + q_mth), (float*)(o + q_pos), (float*)(o + q_nrm),
-                                  (float*)(o + q_max), (float*)(o + q_min), (int32_t*)(o + q_new), (int32_t*)(o + q_idx)};
-    const int rc = triangulate_launch(m, 2, d, cam, 1, pk, c, kcap, (const int32_t*)(p + o_pairs),
-                                      (const int32_t*)(p + o_cnt) + 2, mb, mbf, &dout, s);
+    st.in(&d_matched, matched, 2 * nm, 2 * C);
+    st.in(&d_cnt, &cnt, 1, 1);
+    const int r_new = st.out(&dout.nnew, &out->nnew, 1, 4);
+    const int r_idx = st.out(&dout.new_idx, (int32_t* const*)nullptr, 0, C);  // nnew of them: scattered below
+    st.out(&dout.max_distance, &out->max_distance, nm, C);
+    st.out(&dout.min_distance, &out->min_distance, nm, C);
+    st.out(&dout.pos, &out->pos, 3 * nm, 3 * C);
+    st.out(&dout.normal, &out->normal, 3 * nm, 3 * C);
+    st.out(&dout.reason, &out->reason, nm, C);
+    st.out(&dout.method, &out->method, nm, C);
+    HIP_TRY(st.stage(m->gstage, s));
+    HIP_TRY(st.zero_results(s));
+    d[0].n = &d_cnt->n[0];
+    d[1].n = &d_cnt->n[1];
+    const int rc = triangulate_launch(m, 2, d, cam, 1, pk, c, (int)kcap, d_matched, &d_cnt->nmatched, mb, mbf, &dout, s);
     if (rc) return rc;
-    std::vector<char> h(out_bytes);
-    HIP_TRY(hipMemcpyAsync(h.data(), o, out_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const size_t nm = (size_t)nmatched;
+    HIP_TRY(st.download(s));
     int32_t nnew = 0;
-    std::memcpy(&nnew, h.data() + q_new, 4);
-    if (out->nnew) *out->nnew = nnew;
-    if (out->new_idx && nnew > 0) std::memcpy(out->new_idx, h.data() + q_idx, 4 * (size_t)nnew);
-    if (nm) {
-        if (out->max_distance) std::memcpy(out->max_distance, h.data() + q_max, 4 * nm);
-        if (out->min_distance) std::memcpy(out->min_distance, h.data() + q_min, 4 * nm);
-        if (out->pos) std::memcpy(out->pos, h.data() + q_pos, 12 * nm);
-        if (out->normal) std::memcpy(out->normal, h.data() + q_nrm, 12 * nm);
-        if (out->reason) std::memcpy(out->reason, h.data() + q_rsn, nm);
-        if (out->method) std::memcpy(out->method, h.data() + q_mth, nm);
-    }
+    std::memcpy(&nnew, st.result(r_new), 4);
+    if (out->new_idx && nnew > 0) std::memcpy(out->new_idx, st.result(r_idx), 4 * (size_t)nnew);
     return ORBX_OK;
 }
 

@@ -27,7 +27,6 @@
 // into calls.  The host reads nothing back between setup and the end of a call.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -37,13 +36,10 @@
 #include <vector>
 
 #include "orbx.h"
-#include "orbx_error.h"
+#include "orbx_host.h"
 
 namespace orbx {
 
-int matcher_device(const orbx_matcher* m);          // orbx_matcher.cpp
-hipStream_t matcher_stream(const orbx_matcher* m);
-void matcher_set_last_call_us(orbx_matcher* m, double us);
 
 constexpr int kSim3Threads = 256;
 constexpr int kSim3Waves = kSim3Threads / 64;
@@ -507,8 +503,7 @@ struct orbx_sim3 {
     hipStream_t stream = nullptr;  // the matcher's
     char* work = nullptr;          // Sim3Work arrays
     int32_t* its = nullptr;        // [cap + 1]
-    char* stage = nullptr;         // the single host form's candidate and results
-    size_t stage_cap = 0;
+    orbx::DeviceBuffer stage;      // the single host form's candidate and results
     orbx::Sim3Work W{};
     std::vector<int32_t> h_its;
     // the batch in force (set): what iterate needs
@@ -516,31 +511,15 @@ struct orbx_sim3 {
     int batch = 0, batch_cap = 0, draw_stride = 0, fix_scale = 0, min_inliers = 0;
     float K1[4] = {}, K2[4] = {};
     const int32_t* draws = nullptr;
-    // the single host form's candidate
-    bool host_set = false;
-    int host_n1 = 0;
-    size_t host_out = 0;
+    // the single host form's candidate (set): its result block, the device addresses in it,
+    // and iterate's destinations
+    orbx::HostStage host{orbx::up256};
+    orbx_sim3_result host_dev{}, host_out{};
 };
 
 namespace {
 
 using namespace orbx;
-
-int fail(int code, const char* what) {
-    set_last_error(what);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                               \
-    do {                                                                            \
-        hipError_t _e = (expr);                                                     \
-        if (_e != hipSuccess) {                                                     \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));      \
-            return ORBX_ERR_HIP;                                                    \
-        }                                                                           \
-    } while (0)
-
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // SetRansacParameters (cc:145-181) for N = n, with the host's libm
 int ransac_iterations(int n, int min_inliers, double probability, int max_iterations) {
@@ -555,10 +534,6 @@ int ransac_iterations(int n, int min_inliers, double probability, int max_iterat
     }
     return std::max(1, std::min(its, max_iterations));
 }
-
-// the fixed layout of the single host form's results in the stage
-constexpr size_t kHostInts = 8;  // found, no_more, n_inliers, best_inliers, best_iteration, iterations, n_pairs, status
-constexpr size_t kHostFloats = 16 + 9 + 3 + 1;  // T12, best_R, best_t, best_s
 
 // the argument checks of orbx_sim3_set_batch_device and orbx_sim3_set, before any GPU work
 int check_batch(const orbx_sim3* s, const orbx_sim3_batch* in) {
@@ -599,11 +574,12 @@ int orbx_sim3_create(orbx_matcher* m, int max_batch, int cap, int max_iterations
     s->cap = cap;
     s->max_iterations = max_iterations;
     const size_t slots = (size_t)max_batch * cap;
-    const size_t o_pts = 0, o_thr = o_pts + up256(slots * kSim3Planes * 8), o_idx = o_thr + up256(slots * 2 * 4),
-                 o_state = o_idx + up256(slots * 4), o_counts = o_state + up256((size_t)max_batch * kSim3State * 4),
-                 total = o_counts + up256((size_t)max_batch * max_iterations * 4);
+    Layout L(up256);
+    const size_t o_pts = L.take(slots * kSim3Planes * 8), o_thr = L.take(slots * 2 * 4), o_idx = L.take(slots * 4),
+                 o_state = L.take((size_t)max_batch * kSim3State * 4),
+                 o_counts = L.take((size_t)max_batch * max_iterations * 4);
     hipError_t e = hipSetDevice(s->device);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->work, total);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->work, L.total());
     if (e == hipSuccess) e = hipMalloc((void**)&s->its, ((size_t)cap + 1) * 4);
     if (e != hipSuccess) {
         if (s->work) (void)hipFree(s->work);
@@ -629,7 +605,7 @@ void orbx_sim3_destroy(orbx_sim3* s) {
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     if (s->work) (void)hipFree(s->work);
     if (s->its) (void)hipFree(s->its);
-    if (s->stage) (void)hipFree(s->stage);
+    s->stage.release();
     delete s;
 }
 
@@ -641,7 +617,7 @@ int orbx_sim3_set_batch_device(orbx_sim3* s, const orbx_sim3_batch* in, void* st
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = stream ? (hipStream_t)stream : s->stream;
     s->is_set = false;
-    s->host_set = false;
+    s->host = HostStage(up256);
     if (B == 0) {
         s->batch = 0;
         s->is_set = true;
@@ -721,101 +697,58 @@ int orbx_sim3_set(orbx_sim3* s, const orbx_sim3_batch* in) {
     const int cap = in->cap;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = s->stream;
-    const size_t c4 = up256((size_t)cap * 4), npos = up256((size_t)(in->n_mp > 0 ? in->n_mp : 1) * 12),
-                 ndraw = up256((size_t)in->max_iterations * 12);
-    const size_t o_n1 = 0, o_mp1 = 256, o_mp2 = o_mp1 + c4, o_oct1 = o_mp2 + c4, o_oct2 = o_oct1 + c4,
-                 o_T = o_oct2 + c4, o_pos = o_T + 256, o_draws = o_pos + npos, o_out = o_draws + ndraw,
-                 total = o_out + up256(kHostInts * 4 + kHostFloats * 4 + (size_t)cap);
-    if (s->stage_cap < total) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (s->stage) HIP_TRY(hipFree(s->stage));
-        s->stage = nullptr;
-        s->stage_cap = 0;
-        HIP_TRY(hipMalloc((void**)&s->stage, total));
-        s->stage_cap = total;
-    }
-    char* p = s->stage;
     int n1 = in->n1[0];
     n1 = n1 < 0 ? 0 : (n1 > cap ? cap : n1);
-    // pageable sources: staged by the runtime before each call returns
-    HIP_TRY(hipMemcpyAsync(p + o_n1, in->n1, 4, hipMemcpyHostToDevice, st));
-    if (n1 > 0) {
-        HIP_TRY(hipMemcpyAsync(p + o_mp1, in->mp1, (size_t)n1 * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(p + o_mp2, in->mp2, (size_t)n1 * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(p + o_oct1, in->oct1, (size_t)n1 * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(p + o_oct2, in->oct2, (size_t)n1 * 4, hipMemcpyHostToDevice, st));
-    }
-    float T[24];
-    std::memcpy(T, in->Tcw1, 48);
-    std::memcpy(T + 12, in->Tcw2, 48);
-    HIP_TRY(hipMemcpyAsync(p + o_T, T, sizeof(T), hipMemcpyHostToDevice, st));
-    if (in->n_mp > 0) HIP_TRY(hipMemcpyAsync(p + o_pos, in->mp_pos, (size_t)in->n_mp * 12, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(p + o_draws, in->draws, (size_t)in->max_iterations * 12, hipMemcpyHostToDevice, st));
+    const size_t N = (size_t)n1, C = (size_t)cap, its = (size_t)in->max_iterations;
+    struct {
+        float Tcw1[12], Tcw2[12];
+    } T, *d_T = nullptr;
+    std::memcpy(T.Tcw1, in->Tcw1, sizeof(T.Tcw1));
+    std::memcpy(T.Tcw2, in->Tcw2, sizeof(T.Tcw2));
     orbx_sim3_batch d = *in;
-    d.n1 = (const int32_t*)(p + o_n1);
-    d.mp1 = (const int32_t*)(p + o_mp1);
-    d.mp2 = (const int32_t*)(p + o_mp2);
-    d.oct1 = (const int32_t*)(p + o_oct1);
-    d.oct2 = (const int32_t*)(p + o_oct2);
-    d.Tcw1 = (const float*)(p + o_T);
-    d.Tcw2 = (const float*)(p + o_T) + 12;
-    d.mp_pos = (const float*)(p + o_pos);
-    d.draws = (const int32_t*)(p + o_draws);
+    HostStage h(up256);
+    h.in(&d.n1, in->n1, 1, 1);
+    h.in(&d.mp1, in->mp1, N, C);
+    h.in(&d.mp2, in->mp2, N, C);
+    h.in(&d.oct1, in->oct1, N, C);
+    h.in(&d.oct2, in->oct2, N, C);
+    h.in(&d_T, &T, 1, 1);
+    h.in(&d.mp_pos, in->mp_pos, 3 * (size_t)in->n_mp, 3 * (size_t)(in->n_mp > 0 ? in->n_mp : 1));
+    h.in(&d.draws, in->draws, 3 * its, 3 * its);
+    orbx_sim3_result& r = s->host_dev;
+    const orbx_sim3_result& o = s->host_out;
+    h.out(&r.found, &o.found, 1, 1);
+    h.out(&r.no_more, &o.no_more, 1, 1);
+    h.out(&r.n_inliers, &o.n_inliers, 1, 1);
+    h.out(&r.best_inliers, &o.best_inliers, 1, 1);
+    h.out(&r.best_iteration, &o.best_iteration, 1, 1);
+    h.out(&r.iterations, &o.iterations, 1, 1);
+    h.out(&r.n_pairs, &o.n_pairs, 1, 1);
+    h.out(&r.status, &o.status, 1, 1);
+    h.out(&r.T12, &o.T12, 16, 16);
+    h.out(&r.best_R, &o.best_R, 9, 9);
+    h.out(&r.best_t, &o.best_t, 3, 3);
+    h.out(&r.best_s, &o.best_s, 1, 1);
+    h.out(&r.inliers, &o.inliers, N, C);  // last: iterate downloads up to the n1 in use
+    HIP_TRY(h.stage(s->stage, st));
+    d.Tcw1 = d_T->Tcw1;
+    d.Tcw2 = d_T->Tcw2;
     rc = orbx_sim3_set_batch_device(s, &d, st);
     if (rc) return rc;
-    s->host_set = true;
-    s->host_n1 = n1;
-    s->host_out = o_out;
+    s->host = std::move(h);  // iterate reads the result entries only: they point into the handle
     return ORBX_OK;
 }
 
 int orbx_sim3_iterate(orbx_sim3* s, int n_iterations, const orbx_sim3_result* out) {
     if (!s || !out || n_iterations < 0) return fail(ORBX_ERR_ARG, "bad argument");
-    if (!s->host_set) return fail(ORBX_ERR_STATE, "orbx_sim3_iterate before orbx_sim3_set");
-    const auto t0 = std::chrono::steady_clock::now();
+    if (!s->host.staged()) return fail(ORBX_ERR_STATE, "orbx_sim3_iterate before orbx_sim3_set");
+    CallClock clock(s->matcher);
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = s->stream;
-    char* p = s->stage + s->host_out;
-    int32_t* ints = (int32_t*)p;
-    float* fl = (float*)(p + kHostInts * 4);
-    uint8_t* inl = (uint8_t*)(p + kHostInts * 4 + kHostFloats * 4);
-    orbx_sim3_result d{};
-    d.found = ints;
-    d.no_more = ints + 1;
-    d.n_inliers = ints + 2;
-    d.best_inliers = ints + 3;
-    d.best_iteration = ints + 4;
-    d.iterations = ints + 5;
-    d.n_pairs = ints + 6;
-    d.status = ints + 7;
-    d.T12 = fl;
-    d.best_R = fl + 16;
-    d.best_t = fl + 25;
-    d.best_s = fl + 28;
-    d.inliers = inl;
-    const int rc = orbx_sim3_iterate_device(s, n_iterations, &d, st);
+    const int rc = orbx_sim3_iterate_device(s, n_iterations, &s->host_dev, st);
     if (rc) return rc;
-    const size_t bytes = kHostInts * 4 + kHostFloats * 4 + (size_t)s->host_n1;
-    std::vector<char> h(bytes);
-    HIP_TRY(hipMemcpyAsync(h.data(), p, bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int32_t* hi = (const int32_t*)h.data();
-    const float* hf = (const float*)(h.data() + kHostInts * 4);
-    if (out->found) *out->found = hi[0];
-    if (out->no_more) *out->no_more = hi[1];
-    if (out->n_inliers) *out->n_inliers = hi[2];
-    if (out->best_inliers) *out->best_inliers = hi[3];
-    if (out->best_iteration) *out->best_iteration = hi[4];
-    if (out->iterations) *out->iterations = hi[5];
-    if (out->n_pairs) *out->n_pairs = hi[6];
-    if (out->status) *out->status = hi[7];
-    if (out->T12) std::memcpy(out->T12, hf, 64);
-    if (out->best_R) std::memcpy(out->best_R, hf + 16, 36);
-    if (out->best_t) std::memcpy(out->best_t, hf + 25, 12);
-    if (out->best_s) std::memcpy(out->best_s, hf + 28, 4);
-    if (out->inliers && s->host_n1 > 0) std::memcpy(out->inliers, h.data() + kHostInts * 4 + kHostFloats * 4, (size_t)s->host_n1);
-    matcher_set_last_call_us(s->matcher,
-                             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+    s->host_out = *out;
+    HIP_TRY(s->host.download(st, s->host.results_in_use()));
     return ORBX_OK;
 }
 

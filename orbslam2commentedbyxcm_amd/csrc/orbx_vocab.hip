@@ -35,7 +35,7 @@
 
 #include "orbx.h"
 #include "orbx_block_sort.h"
-#include "orbx_error.h"
+#include "orbx_host.h"
 
 using namespace orbx;
 
@@ -295,20 +295,6 @@ int vocabulary_device(const orbx_vocabulary* v) { return v->device; }
 
 namespace {
 
-int fail(int code, const char* what) {
-    set_last_error(what);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                               \
-    do {                                                                            \
-        hipError_t _e = (expr);                                                     \
-        if (_e != hipSuccess) {                                                     \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));      \
-            return ORBX_ERR_HIP;                                                    \
-        }                                                                           \
-    } while (0)
-
 struct HostTree {
     int k = 0, L = 0, scoring = 0, weighting = 0;
     std::vector<uint8_t> desc;  // node-major, 32 B
@@ -438,8 +424,6 @@ int reserve_work(orbx_vocabulary* v, size_t bytes) {
     v->work_cap = bytes;
     return ORBX_OK;
 }
-
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int next_pow2(int x) {
     int p = 1;
