@@ -1062,6 +1062,84 @@ int orbx_optimize_sim3_batch_device(orbx_matcher* m, const orbx_optimize_sim3_ba
  * with B = 1, one synchronisation; the same bytes as the batch form gives that candidate. */
 int orbx_optimize_sim3(orbx_matcher* m, const orbx_optimize_sim3_batch* os);
 
+/* ---- Optimizer::LocalBundleAdjustment: batched Schur-complement Levenberg-Marquardt ----
+ * Optimizer::LocalBundleAdjustment (src/Optimizer.cc:586-853) from the assembled graph to the
+ * recovered estimates, as LocalMapping::Run calls it (LocalMapping.cc:75), with the g2o it
+ * runs (OptimizationAlgorithmLevenberg, BlockSolver_6_3 with the Schur complement,
+ * EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ with their analytic Jacobians, the robust
+ * quadratic form of BaseBinaryEdge, RobustKernelHuber, SE3Quat), for B local maps in HBM in one
+ * launch: one persistent workgroup per problem runs optimize(5), the chi2 / depth test,
+ * optimize(10) on the edges that passed and the final test.  The covisibility walk that
+ * chooses the keyframes and points (cc:526-583) stays with the caller, as do the erasure of
+ * the flagged observations and UpdateNormalAndDepth (cc:828-853).  The stop flag (pbStopFlag)
+ * is not supported: bDoMore is always true.  Float inputs are widened to double, everything
+ * after is double (but the two float intermediates of the stereo projection), outputs are
+ * rounded to float once.  Every sum has a fixed shape (no floating-point atomics) and no
+ * workgroup waits on another: a problem's results are the same bytes whatever the batch
+ * around it.  The reduced system is factored by a dense unpivoted LDL^T in natural order;
+ * only an exactly zero pivot is a failed solve.  DESIGN.md §4.20.
+ *   Problem b owns rows kf_off[b] .. kf_off[b + 1] of the keyframe table and rows pt_off[b] ..
+ *   pt_off[b + 1] of the point table; point j owns observations obs_off[j] .. obs_off[j + 1]
+ *   (offsets over the whole tables, ascending).  Observation o is keypoint obs_kp[o] of the
+ *   problem's keyframe obs_kf[o] (an index within the problem's rows), whose keypoints are row
+ *   kf_slot[] of kps / u_right.  Edge order is point order, then the order within a point; a
+ *   keyframe appears once among a point's observations.  An observation with an index outside
+ *   its table, or whose keyframe an earlier observation of its point names, is no edge (its flags
+ *   stay 0) and sets
+ *   ORBX_LOCAL_BA_STATUS_BAD_INDEX.
+ *   kf_fixed: lFixedCameras and mnId == 0.  An edge is monocular iff u_right < 0 (cc:679; all
+ *   are when u_right is NULL); information = I * inv_level_sigma2[octave] (octaves clamped
+ *   into [0, nlevels)); the Huber deltas are the floats sqrt(5.991) / sqrt(7.815).
+ *   Outputs: kf_Tcw_opt = Converter::toCvMat(SE3Quat) of every keyframe that is not fixed, the
+ *   input's bytes of a fixed one; pt_pos_opt; erase[o] = vToErase; level1[o] = the edge left
+ *   the second optimisation; n_erase; trace per optimisation {LM iterations, linear solves};
+ *   status = the ORBX_LOCAL_BA_STATUS_* bits.  A problem without a keyframe that may move
+ *   (NO_FREE_KF), or with more of them than min(max_free_kf, ORBX_LOCAL_BA_MAX_FREE_KF)
+ *   (CAPACITY), returns its inputs, no flag set and a zero trace.  An optimisation with no
+ *   active edge, or none at a keyframe that may move, runs no iteration.
+ * inv_level_sigma2 is a host array; every other pointer is a device pointer.  level1 and trace
+ * may be NULL.  Asynchronous on `stream` (or the matcher's). */
+#define ORBX_LOCAL_BA_MAX_FREE_KF 64
+#define ORBX_LOCAL_BA_STATUS_CAPACITY 1
+#define ORBX_LOCAL_BA_STATUS_NO_FREE_KF 2
+#define ORBX_LOCAL_BA_STATUS_BAD_INDEX 4
+typedef struct {
+    int batch;
+    const int32_t* kf_off;           /* [B + 1] */
+    int n_kf;                        /* rows of the keyframe table */
+    const float* kf_Tcw;             /* [n_kf][12] GetPose(), rows 0..2 */
+    const uint8_t* kf_fixed;         /* [n_kf] */
+    const int32_t* kf_slot;          /* [n_kf] row of kps / u_right */
+    const int32_t* pt_off;           /* [B + 1] */
+    int n_pt;                        /* rows of the point table */
+    const float* pt_pos;             /* [n_pt][3] GetWorldPos() */
+    const int32_t* obs_off;          /* [n_pt + 1] */
+    int n_obs;
+    const int32_t* obs_kf;           /* [n_obs] */
+    const int32_t* obs_kp;           /* [n_obs] */
+    int n_slots, cap;
+    const orbx_keypoint* kps;        /* [n_slots][cap] mvKeysUn */
+    const float* u_right;            /* [n_slots][cap] mvuRight, or NULL */
+    const float* inv_level_sigma2;   /* host: mvInvLevelSigma2 (nlevels) */
+    int nlevels;
+    float fx, fy, cx, cy, bf;
+    int max_free_kf;                 /* keyframes that may move per problem that the workspace is
+                                        sized for; 0: ORBX_LOCAL_BA_MAX_FREE_KF */
+    float* kf_Tcw_opt;               /* [n_kf][12] out */
+    float* pt_pos_opt;               /* [n_pt][3] out */
+    uint8_t* erase;                  /* [n_obs] out */
+    uint8_t* level1;                 /* [n_obs] out or NULL */
+    int32_t* n_erase;                /* [B] out */
+    int32_t* trace;                  /* [B][2][2] out or NULL */
+    int32_t* status;                 /* [B] out */
+} orbx_local_ba_batch;
+int orbx_local_bundle_adjustment_batch_device(orbx_matcher* m, const orbx_local_ba_batch* lba, void* stream);
+
+/* The single-problem host form: every pointer of the struct is a host pointer and batch is 1
+ * (kf_off = {0, n_kf}, pt_off = {0, n_pt}).  One upload, the batch kernel with B = 1, one
+ * synchronisation; the same bytes as the batch form gives that problem. */
+int orbx_local_bundle_adjustment(orbx_matcher* m, const orbx_local_ba_batch* lba);
+
 /* ---- LocalMapping::CreateNewMapPoints: triangulation and tests of the matched pairs ----
  * The second half of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:307-501) for the
  * vMatchedPairs that orbx_search_for_triangulation_batch_device left in HBM, with

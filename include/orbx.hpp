@@ -237,8 +237,8 @@ inline void ComputeStereoFromRGBD(const orbx_camera& cam, const std::vector<orbx
                                         mDepthMapFactor, mbf, mvKeysUn.data(), mvuRight.data(), mvDepth.data()));
 }
 
-// Optimizer (include/Optimizer.h): the g2o call on the per-frame path and the one of
-// LoopClosing::ComputeSim3.
+// Optimizer (include/Optimizer.h): the g2o call on the per-frame path, the one of
+// LoopClosing::ComputeSim3 and the one of LocalMapping::Run.
 // PoseOptimization(Frame*) (src/Optimizer.cc:299-502) on the Frame's arrays: mvKeysUn,
 // mvuRight (empty: monocular), mvpMapPoints as MapPoint ids (-1 = NULL) into the positions
 // mpPos (GetWorldPos(), 3 floats per id), mvInvLevelSigma2, fx fy cx cy mbf and mTcw (rows
@@ -329,6 +329,73 @@ public:
         if (nCorrespondences) *nCorrespondences = counts[1];
         if (nBad) *nBad = counts[2];
         return counts[0];
+    }
+
+    // LocalBundleAdjustment(pKF, pbStopFlag, pMap) (src/Optimizer.cc:586-853) from the assembled
+    // graph on: the local keyframes' and fixed cameras' poses kfTcw (12 floats each, rows 0..2),
+    // kfFixed (lFixedCameras and mnId == 0), kfSlot (each keyframe's row of mvKeysUn / mvuRight,
+    // `cap` keypoints per row; mvuRight empty: monocular), the local points mpPos (3 floats
+    // each), and per point (obsOff, CSR) its observations as (keyframe index obsKF, keypoint
+    // index obsKP).  The covisibility walk stays with the caller and the stop flag is not
+    // supported.  kfTcw and mpPos are updated in place as SetPose / SetWorldPos do; vToErase
+    // gets one flag per observation; returns their number.  trace (optional, 4 ints): per
+    // optimisation the LM iterations run and the linear solves tried; status (optional): the
+    // ORBX_LOCAL_BA_STATUS_* bits.
+    static int LocalBundleAdjustment(ORBmatcher& matcher, std::vector<float>& kfTcw, const std::vector<uint8_t>& kfFixed,
+                                     const std::vector<int32_t>& kfSlot, std::vector<float>& mpPos,
+                                     const std::vector<int32_t>& obsOff, const std::vector<int32_t>& obsKF,
+                                     const std::vector<int32_t>& obsKP, const std::vector<orbx_keypoint>& mvKeysUn,
+                                     const std::vector<float>& mvuRight, int cap,
+                                     const std::vector<float>& mvInvLevelSigma2, float fx, float fy, float cx, float cy,
+                                     float mbf, std::vector<uint8_t>& vToErase, int32_t* trace = nullptr,
+                                     int* status = nullptr, std::vector<uint8_t>* level1 = nullptr) {
+        const int32_t nkf = (int32_t)kfFixed.size(), npt = (int32_t)(mpPos.size() / 3), nobs = (int32_t)obsKF.size();
+        if (cap <= 0 || kfTcw.size() != (size_t)nkf * 12 || kfSlot.size() != (size_t)nkf ||
+            obsOff.size() != (size_t)npt + 1 || obsKP.size() != (size_t)nobs || mvKeysUn.size() % (size_t)cap ||
+            (!mvuRight.empty() && mvuRight.size() != mvKeysUn.size()))
+            throw std::runtime_error("LocalBundleAdjustment: array sizes differ");
+        const int32_t kf_off[2] = {0, nkf}, pt_off[2] = {0, npt};
+        std::vector<float> Tout(kfTcw.size()), Xout(mpPos.size());
+        vToErase.assign((size_t)nobs, 0);
+        if (level1) level1->assign((size_t)nobs, 0);
+        int32_t n_erase = 0, st = 0;
+        orbx_local_ba_batch q{};
+        q.batch = 1;
+        q.kf_off = kf_off;
+        q.n_kf = nkf;
+        q.kf_Tcw = kfTcw.data();
+        q.kf_fixed = kfFixed.data();
+        q.kf_slot = kfSlot.data();
+        q.pt_off = pt_off;
+        q.n_pt = npt;
+        q.pt_pos = mpPos.data();
+        q.obs_off = obsOff.data();
+        q.n_obs = nobs;
+        q.obs_kf = obsKF.data();
+        q.obs_kp = obsKP.data();
+        q.n_slots = (int)(mvKeysUn.size() / (size_t)cap);
+        q.cap = cap;
+        q.kps = mvKeysUn.data();
+        q.u_right = mvuRight.empty() ? nullptr : mvuRight.data();
+        q.inv_level_sigma2 = mvInvLevelSigma2.data();
+        q.nlevels = (int)mvInvLevelSigma2.size();
+        q.fx = fx;
+        q.fy = fy;
+        q.cx = cx;
+        q.cy = cy;
+        q.bf = mbf;
+        q.kf_Tcw_opt = Tout.data();
+        q.pt_pos_opt = Xout.data();
+        q.erase = vToErase.data();
+        q.level1 = level1 ? level1->data() : nullptr;
+        q.n_erase = &n_erase;
+        q.trace = trace;
+        q.status = &st;
+        check(orbx_local_bundle_adjustment(matcher.handle(), &q));
+        kfTcw = Tout;
+        mpPos = Xout;
+        if (status) *status = st;
+        return n_erase;
     }
 };
 

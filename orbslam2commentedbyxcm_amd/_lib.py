@@ -59,6 +59,7 @@ EXPORTED = [
     "orbx_sim3_create", "orbx_sim3_destroy", "orbx_sim3_set_batch_device", "orbx_sim3_iterate_device", "orbx_sim3_set",
     "orbx_sim3_iterate", "orbx_sim3_draws", "orbx_optimize_sim3_batch_device", "orbx_optimize_sim3",
     "orbx_triangulate_pairs_batch_device", "orbx_triangulate_pairs",
+    "orbx_local_bundle_adjustment_batch_device", "orbx_local_bundle_adjustment",
     "orbx_initializer_create", "orbx_initializer_destroy", "orbx_initializer_initialize_device",
     "orbx_initializer_initialize", "orbx_initializer_sets",
 ]
@@ -161,6 +162,24 @@ class OptimizeSim3Batch(C.Structure):
                 ("th2", C.c_float), ("fix_scale", C.c_int), ("R12_opt", C.c_void_p), ("t12_opt", C.c_void_p),
                 ("s12_opt", C.c_void_p), ("ninliers", C.c_void_p), ("ncorr", C.c_void_p), ("nbad", C.c_void_p),
                 ("trace", C.c_void_p)]
+
+
+class LocalBaBatch(C.Structure):
+    """orbx_local_ba_batch."""
+    _fields_ = [("batch", C.c_int), ("kf_off", C.c_void_p), ("n_kf", C.c_int), ("kf_Tcw", C.c_void_p),
+                ("kf_fixed", C.c_void_p), ("kf_slot", C.c_void_p), ("pt_off", C.c_void_p), ("n_pt", C.c_int),
+                ("pt_pos", C.c_void_p), ("obs_off", C.c_void_p), ("n_obs", C.c_int), ("obs_kf", C.c_void_p),
+                ("obs_kp", C.c_void_p), ("n_slots", C.c_int), ("cap", C.c_int), ("kps", C.c_void_p),
+                ("u_right", C.c_void_p), ("inv_level_sigma2", C.POINTER(C.c_float)), ("nlevels", C.c_int),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float),
+                ("max_free_kf", C.c_int), ("kf_Tcw_opt", C.c_void_p), ("pt_pos_opt", C.c_void_p), ("erase", C.c_void_p),
+                ("level1", C.c_void_p), ("n_erase", C.c_void_p), ("trace", C.c_void_p), ("status", C.c_void_p)]
+
+
+ORBX_LOCAL_BA_MAX_FREE_KF = 64
+ORBX_LOCAL_BA_STATUS_CAPACITY = 1
+ORBX_LOCAL_BA_STATUS_NO_FREE_KF = 2
+ORBX_LOCAL_BA_STATUS_BAD_INDEX = 4
 
 
 class KeyFrameGeomDevice(C.Structure):
@@ -403,6 +422,8 @@ def lib() -> C.CDLL:
     L.orbx_sim3_draws.argtypes = [i32p, C.c_int, C.c_int]
     L.orbx_optimize_sim3_batch_device.argtypes = [vp, C.POINTER(OptimizeSim3Batch), vp]
     L.orbx_optimize_sim3.argtypes = [vp, C.POINTER(OptimizeSim3Batch)]
+    L.orbx_local_bundle_adjustment_batch_device.argtypes = [vp, C.POINTER(LocalBaBatch), vp]
+    L.orbx_local_bundle_adjustment.argtypes = [vp, C.POINTER(LocalBaBatch)]
     L.orbx_triangulate_pairs_batch_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, i32p, C.c_int, vp, vp, C.c_float,
                                                       C.c_float, C.POINTER(NewMapPoints), vp]
     L.orbx_triangulate_pairs.argtypes = [vp, C.POINTER(KeyFrameGeomDevice), C.POINTER(KeyFrameGeomDevice), vp, C.c_int,

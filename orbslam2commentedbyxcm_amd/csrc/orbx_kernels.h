@@ -183,6 +183,56 @@ struct OptSim3Args {
 size_t opt_sim3_workspace_bytes(int batch, int cap1);
 hipError_t launch_opt_sim3(OptSim3Args A, int batch, char* workspace, hipStream_t stream);
 
+// k_local_ba (orbx_localba.hip): Optimizer::LocalBundleAdjustment for `batch` local maps, one
+// workgroup each; poses, points, edge records, the per-point blocks and the reduced system S
+// live in the workspace.
+struct LocalBaArgs {
+    const int32_t* kf_off;       // [B + 1]
+    int n_kf;
+    const float* kf_Tcw;         // [n_kf][12]
+    const uint8_t* kf_fixed;     // [n_kf]
+    const int32_t* kf_slot;      // [n_kf]
+    const int32_t* pt_off;       // [B + 1]
+    int n_pt;
+    const float* pt_pos;         // [n_pt][3]
+    const int32_t* obs_off;      // [n_pt + 1]
+    int n_obs;
+    const int32_t* obs_kf;       // [n_obs]
+    const int32_t* obs_kp;       // [n_obs]
+    int n_slots, cap;
+    const orbx_keypoint* kps;    // [n_slots][cap]
+    const float* u_right;        // [n_slots][cap] or null
+    float inv_sigma2[ORBX_MAX_LEVELS];
+    int nlevels;
+    float fx, fy, cx, cy, bf;
+    float delta_mono, delta_stereo;
+    int max_free;                // free keyframes per problem that S is sized for
+    float* kf_Tcw_out;           // [n_kf][12]
+    float* pt_pos_out;           // [n_pt][3]
+    uint8_t* erase;              // [n_obs]
+    uint8_t* level1;             // [n_obs] or null
+    int32_t* n_erase;            // [B]
+    int32_t* trace;              // [B][2][2] or null
+    int32_t* status;             // [B]
+    // set by launch_local_ba
+    double* pose;                // [n_kf][2][16]: current and trial {q xyzw, t, R row by row}
+    double* pt;                  // [n_pt][2][3]: current and trial
+    double* pt_sys;              // [n_pt][24]: Hll (6), bl (3), Dinv (9), Dinv bl (3), xl (3)
+    double* W;                   // [n_obs][18]: A^T (rho' Omega) B
+    double* chi2;                // [n_obs]
+    double* S;                   // [B][(6 max_free)^2]
+    float* rec;                  // [n_obs][4]: u, v, u_right, invSigma2
+    int32_t* rec_kf;             // [n_obs] keyframe row, -1: not an edge
+    int32_t* rec_pt;             // [n_obs] point row
+    int32_t* rec_flags;          // [n_obs]
+    int32_t* rec_free;           // [n_obs] column block in S, -1: none this phase
+    int32_t* kf_free;            // [n_kf] column block in S, -1: none this phase
+    int32_t* kf_elist;           // [n_obs] the edges of each free keyframe, in edge order
+    int32_t* pt_active;          // [n_pt]
+};
+size_t local_ba_workspace_bytes(int batch, int n_kf, int n_pt, int n_obs, int max_free);
+hipError_t launch_local_ba(LocalBaArgs A, int batch, char* workspace, hipStream_t stream);
+
 // k_triangulate_pairs (orbx_triangulate.hip): LocalMapping::CreateNewMapPoints' triangulation
 // and tests (LocalMapping.cc:307-501) over the matched pairs of `npairs` keyframe pairs, one
 // workgroup each.

@@ -2197,6 +2197,116 @@ int orbx_optimize_sim3(orbx_matcher* m, const orbx_optimize_sim3_batch* os) {
     return ORBX_OK;
 }
 
+static const char* local_ba_check(const orbx_local_ba_batch* q) {
+    if (q->batch < 0 || q->n_kf < 0 || q->n_pt < 0 || q->n_obs < 0 || q->n_slots < 0 || q->cap <= 0 ||
+        q->nlevels < 1 || q->nlevels > ORBX_MAX_LEVELS || q->max_free_kf < 0)
+        return "bad argument";
+    if (!q->inv_level_sigma2) return "null host array";
+    if (q->batch == 0) return nullptr;
+    if (!q->kf_off || !q->pt_off || !q->obs_off || !q->n_erase || !q->status) return "null buffer";
+    if (q->n_kf > 0 && (!q->kf_Tcw || !q->kf_fixed || !q->kf_slot || !q->kf_Tcw_opt)) return "null keyframe table";
+    if (q->n_pt > 0 && (!q->pt_pos || !q->pt_pos_opt)) return "null point table";
+    if (q->n_obs > 0 && (!q->obs_kf || !q->obs_kp || !q->erase || !q->kps)) return "null observation table";
+    if (q->n_kf >= (1 << 24) || q->n_pt >= (1 << 26) || q->n_obs >= (1 << 26)) return "table too large";
+    if ((size_t)q->n_slots * (size_t)q->cap >= ((size_t)1 << 31)) return "n_slots x cap of 2^31 or more";
+    return nullptr;
+}
+
+// Optimizer::LocalBundleAdjustment for a batch of local maps in HBM (see include/orbx.h)
+int orbx_local_bundle_adjustment_batch_device(orbx_matcher* m, const orbx_local_ba_batch* q, void* stream) {
+    if (!m || !q) return fail(ORBX_ERR_ARG, "null argument");
+    if (const char* why = local_ba_check(q)) return fail(ORBX_ERR_ARG, why);
+    const int B = q->batch;
+    if (B == 0) return ORBX_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+    LocalBaArgs A{};
+    A.max_free = q->max_free_kf > 0 && q->max_free_kf < ORBX_LOCAL_BA_MAX_FREE_KF ? q->max_free_kf
+                                                                                    : ORBX_LOCAL_BA_MAX_FREE_KF;
+    HIP_TRY(m->pscr.reserve(local_ba_workspace_bytes(B, q->n_kf, q->n_pt, q->n_obs, A.max_free), s));
+    A.kf_off = q->kf_off;
+    A.n_kf = q->n_kf;
+    A.kf_Tcw = q->kf_Tcw;
+    A.kf_fixed = q->kf_fixed;
+    A.kf_slot = q->kf_slot;
+    A.pt_off = q->pt_off;
+    A.n_pt = q->n_pt;
+    A.pt_pos = q->pt_pos;
+    A.obs_off = q->obs_off;
+    A.n_obs = q->n_obs;
+    A.obs_kf = q->obs_kf;
+    A.obs_kp = q->obs_kp;
+    A.n_slots = q->n_slots;
+    A.cap = q->cap;
+    A.kps = q->kps;
+    A.u_right = q->u_right;
+    for (int l = 0; l < q->nlevels; l++) A.inv_sigma2[l] = q->inv_level_sigma2[l];
+    A.nlevels = q->nlevels;
+    A.fx = q->fx;
+    A.fy = q->fy;
+    A.cx = q->cx;
+    A.cy = q->cy;
+    A.bf = q->bf;
+    A.delta_mono = (float)std::sqrt(5.991);    // Optimizer.cc:650
+    A.delta_stereo = (float)std::sqrt(7.815);  // Optimizer.cc:653
+    A.kf_Tcw_out = q->kf_Tcw_opt;
+    A.pt_pos_out = q->pt_pos_opt;
+    A.erase = q->erase;
+    A.level1 = q->level1;
+    A.n_erase = q->n_erase;
+    A.trace = q->trace;
+    A.status = q->status;
+    HIP_TRY(launch_local_ba(A, B, m->pscr.p, s));
+    return ORBX_OK;
+}
+
+// The single-problem host form: one staged problem, the batch kernel, one synchronisation.
+int orbx_local_bundle_adjustment(orbx_matcher* m, const orbx_local_ba_batch* q) {
+    if (!m || !q) return fail(ORBX_ERR_ARG, "null argument");
+    if (q->batch != 1) return fail(ORBX_ERR_ARG, "the host form takes one problem");
+    if (const char* why = local_ba_check(q)) return fail(ORBX_ERR_ARG, why);
+    if (q->kf_off[0] != 0 || q->kf_off[1] != q->n_kf || q->pt_off[0] != 0 || q->pt_off[1] != q->n_pt)
+        return fail(ORBX_ERR_ARG, "the host form's offsets are {0, n_kf} and {0, n_pt}");
+    if (q->n_pt > 0 && (q->obs_off[0] != 0 || q->obs_off[q->n_pt] != q->n_obs))
+        return fail(ORBX_ERR_ARG, "obs_off does not span the observations");
+    CallClock clock(m);
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    const size_t nk = (size_t)q->n_kf, np = (size_t)q->n_pt, no = (size_t)q->n_obs;
+    const size_t ck = nk ? nk : 1, cp = np ? np : 1, co = no ? no : 1;
+    const size_t nkp = (size_t)q->n_slots * (size_t)q->cap, ckp = nkp ? nkp : 1;
+    struct {
+        int32_t kf_off[2], pt_off[2];
+    } in{{0, q->n_kf}, {0, q->n_pt}}, *d_in = nullptr;
+    const int32_t zero = 0;
+    orbx_local_ba_batch d = *q;
+    HostStage st(pad);
+    st.out(&d.n_erase, &q->n_erase, 1, 1);
+    st.out(&d.status, &q->status, 1, 1);
+    st.out(&d.trace, &q->trace, 4, 4);
+    st.out(&d.kf_Tcw_opt, &q->kf_Tcw_opt, 12 * nk, 12 * ck);
+    st.out(&d.pt_pos_opt, &q->pt_pos_opt, 3 * np, 3 * cp);
+    st.out(&d.erase, &q->erase, no, co);
+    st.out(&d.level1, &q->level1, no, co);
+    st.in(&d.kf_Tcw, q->kf_Tcw, 12 * nk, 12 * ck);
+    st.in(&d.kf_fixed, q->kf_fixed, nk, ck);
+    st.in(&d.kf_slot, q->kf_slot, nk, ck);
+    st.in(&d.pt_pos, q->pt_pos, 3 * np, 3 * cp);
+    st.in(&d.obs_off, np ? (const void*)q->obs_off : (const void*)&zero, np + 1, cp + 1);
+    st.in(&d.obs_kf, q->obs_kf, no, co);
+    st.in(&d.obs_kp, q->obs_kp, no, co);
+    st.in(&d.kps, q->kps, nkp, ckp);
+    st.in_optional(&d.u_right, q->u_right, nkp, ckp);
+    st.in(&d_in, &in, 1, 1);
+    HIP_TRY(st.stage(m->pstage, s));
+    d.kf_off = d_in->kf_off;
+    d.pt_off = d_in->pt_off;
+    const int rc = orbx_local_bundle_adjustment_batch_device(m, &d, s);
+    if (rc) return rc;
+    HIP_TRY(st.download(s));
+    return ORBX_OK;
+}
+
 static const char* triangulate_check(int nkf, const orbx_keyframe_geom_device* kfs, const orbx_frame_view* cam,
                                      int npairs, const int32_t* pairs, int cap, const int32_t* d_pairs,
                                      const int32_t* d_npairs, const orbx_new_mappoints* out) {

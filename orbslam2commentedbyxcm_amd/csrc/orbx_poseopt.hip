@@ -46,95 +46,21 @@ constexpr int kRecWords = 8;  // Xw[3], u, v, u_right, invSigma2, flags
 constexpr int kFlagStereo = 1, kFlagOutlier = 2;
 
 using lm::huber;
+using lm::Pose;
+using lm::pose_map;
+using lm::pose_update;
 using lm::quat_from_matrix;
+using lm::quat_normalize;
 using lm::quat_rotate;
-
-struct Pose {
-    double qx, qy, qz, qw, tx, ty, tz;
-};
 
 struct Cam {
     double fx, fy, cx, cy, bf;
     double delta_mono, delta_stereo;  // the float sqrt(5.991) and sqrt(7.815) of Optimizer.cc:332-334, widened
 };
 
-// SE3Quat::normalizeRotation, se3quat.h:280-285
-__device__ __forceinline__ void quat_normalize(double& x, double& y, double& z, double& w) {
-    if (w < 0) {
-        x = -x;
-        y = -y;
-        z = -z;
-        w = -w;
-    }
-    const double n = sqrt(x * x + y * y + z * z + w * w);
-    x = x / n;
-    y = y / n;
-    z = z / n;
-    w = w / n;
-}
-
-// SE3Quat::map, se3quat.h:217-220
-__device__ __forceinline__ void pose_map(const Pose& P, double X, double Y, double Z, double& x, double& y,
-                                         double& z) {
-    quat_rotate(P.qx, P.qy, P.qz, P.qw, X, Y, Z, x, y, z);
-    x += P.tx;
-    y += P.ty;
-    z += P.tz;
-}
-
 // Eigen's toRotationMatrix
 __device__ __forceinline__ void quat_to_matrix(const Pose& P, double (&R)[3][3]) {
     lm::quat_to_matrix(P.qx, P.qy, P.qz, P.qw, R);
-}
-
-// SE3Quat::exp(x) * P: types_six_dof_expmap.h:73-76 with se3quat.h:223-257 and 104-110
-__device__ __forceinline__ Pose pose_update(const double (&x)[6], const Pose& P) {
-    const double w0 = x[0], w1 = x[1], w2 = x[2];
-    const double theta = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
-    const double O[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
-    double O2[3][3], R[3][3], V[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) O2[i][j] = O[i][0] * O[0][j] + O[i][1] * O[1][j] + O[i][2] * O[2][j];
-    if (theta < 0.00001) {
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                R[i][j] = (i == j ? 1.0 : 0.0) + O[i][j] + O2[i][j];
-                V[i][j] = R[i][j];
-            }
-    } else {
-        const double s = sin(theta), c = cos(theta);
-        const double a = s / theta, b = (1.0 - c) / (theta * theta), d = (theta - s) / (theta * theta * theta);
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                const double id = i == j ? 1.0 : 0.0;
-                R[i][j] = id + a * O[i][j] + b * O2[i][j];
-                V[i][j] = id + b * O[i][j] + d * O2[i][j];
-            }
-    }
-    double q[4];
-    quat_from_matrix(R, q);
-    quat_normalize(q[0], q[1], q[2], q[3]);
-    const double t0 = V[0][0] * x[3] + V[0][1] * x[4] + V[0][2] * x[5];
-    const double t1 = V[1][0] * x[3] + V[1][1] * x[4] + V[1][2] * x[5];
-    const double t2 = V[2][0] * x[3] + V[2][1] * x[4] + V[2][2] * x[5];
-    Pose out;
-    out.qx = q[3] * P.qx + q[0] * P.qw + q[1] * P.qz - q[2] * P.qy;
-    out.qy = q[3] * P.qy + q[1] * P.qw + q[2] * P.qx - q[0] * P.qz;
-    out.qz = q[3] * P.qz + q[2] * P.qw + q[0] * P.qy - q[1] * P.qx;
-    out.qw = q[3] * P.qw - q[0] * P.qx - q[1] * P.qy - q[2] * P.qz;
-    quat_normalize(out.qx, out.qy, out.qz, out.qw);
-    double rx, ry, rz;
-    quat_rotate(q[0], q[1], q[2], q[3], P.tx, P.ty, P.tz, rx, ry, rz);
-    out.tx = rx + t0;
-    out.ty = ry + t1;
-    out.tz = rz + t2;
-    return out;
 }
 
 struct Edge {

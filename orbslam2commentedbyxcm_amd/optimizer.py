@@ -1,12 +1,14 @@
-"""Optimizer::PoseOptimization and Optimizer::OptimizeSim3 on the GPU (include/orbx.h,
-csrc/orbx_poseopt.hip, csrc/orbx_optsim3.hip).
+"""Optimizer::PoseOptimization, Optimizer::OptimizeSim3 and Optimizer::LocalBundleAdjustment on
+the GPU (include/orbx.h, csrc/orbx_poseopt.hip, csrc/orbx_optsim3.hip, csrc/orbx_localba.hip).
 
 PoseOptimizer mirrors the one g2o call on ORB-SLAM2's per-frame path
 (src/Optimizer.cc:299-502): PoseOptimization for one frame on host arrays, and
 pose_optimization_batch_device for B frames in HBM with the callers' epilogue
 (Tracking.cc:1004-1017).  Sim3Optimizer mirrors the one of LoopClosing::ComputeSim3
 (src/Optimizer.cc:1173-1358): OptimizeSim3 for one loop candidate on host arrays, and
-optimize_sim3_batch_device for B candidates in HBM.
+optimize_sim3_batch_device for B candidates in HBM.  LocalBundleAdjuster mirrors the one of
+LocalMapping::Run (src/Optimizer.cc:586-853): LocalBundleAdjustment for one local map on host
+arrays, and local_ba_batch_device for B local maps in HBM.
 """
 from __future__ import annotations
 
@@ -272,3 +274,83 @@ class Sim3Optimizer:
         """Keypoints per row of a (B, cap2) structured or (B, cap2 * 28) byte tensor."""
         cols = int(d_kps2.shape[1])
         return cols // 28 if d_kps2.element_size() == 1 else cols
+
+
+class LocalBundleAdjuster(PoseOptimizer):
+    """Optimizer::LocalBundleAdjustment (src/Optimizer.cc:586-853) on the GPU
+    (csrc/orbx_localba.hip): LocalBundleAdjustment for one local map on host arrays and
+    local_ba_batch_device for B local maps in HBM.  The covisibility walk that chooses the
+    keyframes and points stays with the caller; the stop flag is not supported.  The handle,
+    close() and last_call_us() are PoseOptimizer's."""
+
+    def LocalBundleAdjustment(self, kf_Tcw, kf_fixed, kf_slot, pt_pos, obs_off, obs_kf, obs_kp, keys_un, u_right,
+                              inv_level_sigma2, fx, fy, cx, cy, bf, max_free_kf: int = 0) -> dict:
+        """One local map on host arrays: kf_Tcw (K, 12) f32, kf_fixed (K,) (lFixedCameras and
+        mnId == 0), kf_slot (K,) rows of keys_un / u_right, pt_pos (P, 3) f32, obs_off (P + 1,),
+        obs_kf / obs_kp (n_obs,) (keyframe within the K rows, keypoint within its row),
+        keys_un (n_slots, cap) KEYPOINT_DTYPE, u_right (n_slots, cap) f32 or None.
+        Returns Tcw (K, 12) and pos (P, 3) f32, erase and level1 (n_obs,) u8, n_erase,
+        trace (2, 2) i32 and status."""
+        T = _f32(kf_Tcw).reshape(-1, 12)
+        fixed = np.ascontiguousarray(kf_fixed, dtype=np.uint8)
+        slot = np.ascontiguousarray(kf_slot, dtype=np.int32)
+        pos = _f32(pt_pos).reshape(-1, 3)
+        off = np.ascontiguousarray(obs_off, dtype=np.int32)
+        okf = np.ascontiguousarray(obs_kf, dtype=np.int32)
+        okp = np.ascontiguousarray(obs_kp, dtype=np.int32)
+        keys = np.ascontiguousarray(keys_un, dtype=L.KEYPOINT_DTYPE)
+        if keys.ndim != 2:
+            raise ValueError("keys_un must be (n_slots, cap)")
+        ur = None if u_right is None else _f32(u_right)
+        K, P, no = len(T), len(pos), len(okf)
+        if len(fixed) != K or len(slot) != K or len(off) != P + 1 or len(okp) != no or \
+                (ur is not None and ur.shape != keys.shape):
+            raise ValueError("table sizes differ")
+        sig = _f32(inv_level_sigma2)
+        kf_off = np.array([0, K], np.int32)
+        pt_off = np.array([0, P], np.int32)
+        out = dict(Tcw=np.zeros((K, 12), np.float32), pos=np.zeros((P, 3), np.float32), erase=np.zeros(no, np.uint8),
+                   level1=np.zeros(no, np.uint8), trace=np.zeros((2, 2), np.int32))
+        n_erase, status = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+        q = L.LocalBaBatch()
+        q.batch = 1
+        q.kf_off, q.n_kf, q.kf_Tcw, q.kf_fixed, q.kf_slot = ptr(kf_off), K, ptr(T), ptr(fixed), ptr(slot)
+        q.pt_off, q.n_pt, q.pt_pos = ptr(pt_off), P, ptr(pos)
+        q.obs_off, q.n_obs, q.obs_kf, q.obs_kp = ptr(off), no, ptr(okf), ptr(okp)
+        q.n_slots, q.cap, q.kps, q.u_right = keys.shape[0], keys.shape[1], ptr(keys), ptr(ur)
+        q.inv_level_sigma2, q.nlevels = sig.ctypes.data_as(F32P), len(sig)
+        q.fx, q.fy, q.cx, q.cy, q.bf = fx, fy, cx, cy, bf
+        q.max_free_kf = int(max_free_kf)
+        q.kf_Tcw_opt, q.pt_pos_opt, q.erase, q.level1 = ptr(out["Tcw"]), ptr(out["pos"]), ptr(out["erase"]), ptr(out["level1"])
+        q.n_erase, q.trace, q.status = ptr(n_erase), ptr(out["trace"]), ptr(status)
+        L.check(L.lib().orbx_local_bundle_adjustment(self._h, C.byref(q)))
+        out["n_erase"], out["status"] = int(n_erase[0]), int(status[0])
+        return out
+
+    def local_ba_batch_device(self, d_kf_off, d_kf_Tcw, d_kf_fixed, d_kf_slot, d_pt_off, d_pt_pos, d_obs_off, d_obs_kf,
+                              d_obs_kp, d_kps, d_u_right, inv_level_sigma2, fx, fy, cx, cy, bf, d_kf_Tcw_opt,
+                              d_pt_pos_opt, d_erase, d_n_erase, d_status, d_level1=None, d_trace=None,
+                              max_free_kf: int = 0, stream=None) -> None:
+        """orbx_local_bundle_adjustment_batch_device on device tensors: d_kf_off / d_pt_off
+        (B + 1,) i32, d_kf_Tcw / d_kf_Tcw_opt (n_kf, 12) f32, d_kf_fixed (n_kf,) u8, d_kf_slot
+        (n_kf,) i32, d_pt_pos / d_pt_pos_opt (n_pt, 3) f32, d_obs_off (n_pt + 1,) i32, d_obs_kf /
+        d_obs_kp (n_obs,) i32, d_kps (n_slots, cap) keypoints (any 28-byte layout), d_u_right
+        (n_slots, cap) f32 or None, d_erase / d_level1 (n_obs,) u8, d_n_erase / d_status (B,) i32,
+        d_trace (B, 2, 2) i32.  Asynchronous on `stream` (or the handle's)."""
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        sig = _f32(inv_level_sigma2)
+        q = L.LocalBaBatch()
+        q.batch = int(d_kf_off.shape[0]) - 1
+        q.kf_off, q.n_kf, q.kf_Tcw = ptr(d_kf_off), int(d_kf_Tcw.shape[0]), ptr(d_kf_Tcw)
+        q.kf_fixed, q.kf_slot = ptr(d_kf_fixed), ptr(d_kf_slot)
+        q.pt_off, q.n_pt, q.pt_pos = ptr(d_pt_off), int(d_pt_pos.shape[0]), ptr(d_pt_pos)
+        q.obs_off, q.n_obs, q.obs_kf, q.obs_kp = ptr(d_obs_off), int(d_obs_kf.shape[0]), ptr(d_obs_kf), ptr(d_obs_kp)
+        q.n_slots, q.cap, q.kps, q.u_right = int(d_kps.shape[0]), int(d_kps.shape[1]), ptr(d_kps), ptr(d_u_right)
+        q.inv_level_sigma2, q.nlevels = sig.ctypes.data_as(F32P), len(sig)
+        q.fx, q.fy, q.cx, q.cy, q.bf = fx, fy, cx, cy, bf
+        q.max_free_kf = int(max_free_kf)
+        q.kf_Tcw_opt, q.pt_pos_opt, q.erase, q.level1 = ptr(d_kf_Tcw_opt), ptr(d_pt_pos_opt), ptr(d_erase), ptr(d_level1)
+        q.n_erase, q.trace, q.status = ptr(d_n_erase), ptr(d_trace), ptr(d_status)
+        s = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        L.check(L.lib().orbx_local_bundle_adjustment_batch_device(self._h, C.byref(q), s))
