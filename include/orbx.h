@@ -994,6 +994,152 @@ int orbx_sim3_iterate(orbx_sim3* s, int n_iterations, const orbx_sim3_result* ou
  * reference stops consuming rand() at the returning iteration.  Host only, no GPU. */
 int orbx_sim3_draws(int32_t* draws, int n, int iterations);
 
+/* ---- PnPsolver: EPnP under RANSAC for a batch of relocalisation candidates ----
+ * PnPsolver (include/PnPsolver.h, src/PnPsolver.cc:80-1345) as Tracking::Relocalization drives
+ * it (Tracking.cc:1511-1684: one solver per candidate keyframe, iterate(5) round-robin), for B
+ * candidates in HBM, a candidate being one pair (lost frame, candidate keyframe): the link
+ * between orbx_search_by_bow_frame and orbx_pose_optimization_batch_device.  Float inputs are
+ * widened to double, everything after is double except CheckInliers' mixed precision (below),
+ * poses are rounded to float once per result.  No sum crosses lanes in floating point: a
+ * candidate's results are the same bytes whatever the batch around it and however its
+ * iterations are cut into calls.  The host reads nothing back between a set and the end of
+ * an iterate.  DESIGN.md §4.21.
+ *
+ * What the reference leaves to OpenCV is fixed here (csrc/orbx_epnp.h): the SVDs of the
+ * symmetric 3x3 PW0^T PW0 and 12x12 M^T M are a one-sided cyclic Jacobi on the matrix itself
+ * (pairs (p, q), p < q, in lexicographic order; a pair is rotated unless gamma == 0 or |gamma|
+ * <= 8 eps sqrt(alpha beta); the sweeps end with the first that rotates nothing, at most 30),
+ * values descending with the higher index the smaller on a tie, vectors as the Jacobi leaves
+ * them (no sign normalisation), v[0..3] the vectors of the four smallest values, smallest
+ * first; cvInvert(CC) is rows u_i^T / k_i in closed form (zero where k_i == 0);
+ * cvSolve(CV_SVD) is least squares through the same Jacobi on L, dropping the columns with
+ * |b_j| <= 2 eps sum |b_k|; qr_solve (cc:1211-1345) is restated operation for operation with
+ * its eta == 0 return, the increment starting at 0; estimate_R_and_t's 3x3 SVD is the
+ * Initializer's (u_2 = u_0 x u_1 on b_2's side).  With minimal sets of 4 the hypotheses
+ * depend on these choices; what a call returns after Refine() does not where the keypoints
+ * are exact.
+ *
+ * The library owns no random generator: the caller supplies the four draws of every
+ * iteration (orbx_pnp_draws gives the reference's).
+ *
+ * orbx_pnp_create (the workspace and per-candidate state for up to max_batch candidates of up
+ * to cap slots and max_draws <= ORBX_PNP_MAX_DRAWS iterations with draws) borrows the
+ * matcher's device and stream; the matcher must outlive it.  orbx_pnp_destroy waits for that
+ * stream; after the library's unload destructor it releases nothing. */
+#define ORBX_PNP_MAX_DRAWS 4096
+#define ORBX_PNP_STATUS_BAD_DRAW 1 /* status bit 0: a walked iteration had a draw outside [0, N - j) */
+#define ORBX_PNP_STATUS_NO_DRAWS 2 /* status bit 1: a call ended at an iteration >= n_draws */
+typedef struct orbx_pnp orbx_pnp;
+int orbx_pnp_create(orbx_matcher* m, int max_batch, int cap, int max_draws, orbx_pnp** out);
+void orbx_pnp_destroy(orbx_pnp* s);
+
+/* The constructor (cc:80-128) and SetRansacParameters(probability, min_inliers,
+ * max_iterations, min_set, epsilon, th2) (cc:141-190) for `batch` candidates of one camera.
+ *   Slot i < n of a candidate is kept iff matches[i] (vpMapPointMatches, as
+ *   orbx_search_by_bow_frame writes it: the MapPoint id, -1 for none) lies in [0, n_mp); any
+ *   negative id or one outside the table skips the slot (the caller maps NULL and isBad() to
+ *   -1; cc:96-118).  Kept slots in slot order are the N correspondences (mvKeyPointIndices):
+ *   mvP2D = kps[i].pt (mvKeysUn), mvP3Dw = mp_pos[matches[i]], mvMaxError =
+ *   level_sigma2[octave] * th2 as a float product (cc:189), octaves clamped into [0, nlevels).
+ *   The parameters follow cc:141-183 with their quirks, evaluated by the host's libm for every
+ *   n in 0..cap and looked up on the device at N: mRansacMinInliers = max(int((float)N *
+ *   epsilon), min_inliers, min_set); epsilon is raised to (float)mRansacMinInliers / N;
+ *   mRansacMaxIts = 1 if mRansacMinInliers == N, else ceil(log(1 - p) / log(1 - pow(epsilon,
+ *   3))) (the exponent is 3), clamped with max(1, min(., max_iterations)).  Only min_set == 4
+ *   is accepted (ORBX_ERR_ARG otherwise).  mnIterations and mnBestInliers are reset to 0.
+ *   draws [batch][n_draws][4], n_draws >= max_iterations, is read by the later iterate calls,
+ *   indexed by the absolute iteration, and must stay valid until the next set: draw j of an
+ *   iteration is RandomInt(0, N - 1 - j) (cc:239) and must lie in [0, N - j); otherwise that
+ *   iteration has a NaN hypothesis and 0 inliers, and ORBX_PNP_STATUS_BAD_DRAW is set once it
+ *   is walked.  The four are applied without replacement by the swap-with-last of cc:239-249.
+ * level_sigma2 is a host array, every other pointer is a device pointer (all are host
+ * pointers, and batch is 1, for orbx_pnp_set).  Asynchronous on `stream` (or the matcher's);
+ * the calls on one solver share its workspace, so the caller keeps them in order. */
+typedef struct {
+    int batch;
+    int cap;                    /* slots per candidate row, <= the solver's cap */
+    const orbx_keypoint* kps;   /* [B][cap] F.mvKeysUn */
+    const int32_t* n;           /* [B] vpMapPointMatches.size(), clamped into [0, cap] */
+    const int32_t* matches;     /* [B][cap] vpMapPointMatches as MapPoint ids, -1 = none */
+    int n_mp;                   /* MapPoints in the table */
+    const float* mp_pos;        /* [n_mp][3] GetWorldPos() */
+    const float* level_sigma2;  /* host: F.mvLevelSigma2 (nlevels) */
+    int nlevels;
+    float fx, fy, cx, cy;       /* F.fx F.fy F.cx F.cy */
+    double probability;         /* in (0, 1): 0.99 */
+    int min_inliers;            /* 10 */
+    int max_iterations;         /* 300; <= n_draws */
+    int min_set;                /* 4 */
+    float epsilon;              /* in [0, 1]: 0.5 */
+    float th2;                  /* 5.991 */
+    const int32_t* draws;       /* [B][n_draws][4] */
+    int n_draws;                /* <= the solver's max_draws */
+} orbx_pnp_batch;
+int orbx_pnp_set_batch_device(orbx_pnp* s, const orbx_pnp_batch* in, void* stream);
+
+/* iterate(n_iterations, bNoMore, vbInliers, nInliers) (cc:200-323) on every candidate of the
+ * batch in force; find() (cc:193-197) is n_iterations = max_iterations on a fresh set.  The
+ * loop condition is `mnIterations < mRansacMaxIts || nCurrentIterations < nIterations`
+ * (cc:226, an OR): the first call runs to the iteration cap unless it returns, a later call
+ * runs n_iterations more, beyond the cap.  An iteration whose absolute index is >= n_draws
+ * is not run: the call ends with found 0, no_more 1 and ORBX_PNP_STATUS_NO_DRAWS.
+ *   With inl_k the CheckInliers count of iteration k's hypothesis (compute_pose on its four
+ *   correspondences), the iteration qualifies if inl_k >= mRansacMinInliers; inl_k >
+ *   mnBestInliers then replaces the best state (a tie keeps the earlier iteration; mBestTcw is
+ *   rounded to float there, cc:270-276), and Refine() (cc:326-378) runs compute_pose on
+ *   mvbBestInliers -- the best state's, not the current hypothesis' -- and CheckInliers for
+ *   its pose; it succeeds on a refined count > mRansacMinInliers (strict).  On success the call
+ *   returns found 1, refined 1, the refined Tcw, the refined flags at mvKeyPointIndices and
+ *   their count; no_more stays 0.  Refine is a function of the best state alone, so its
+ *   result is computed when the best state changes and reused by later qualifying iterations
+ *   (a success is returned again by the next qualifying iteration, as the reference does).
+ *   A call that ends without that return gives no_more = mnIterations >= mRansacMaxIts, and
+ *   then, if mnBestInliers >= mRansacMinInliers, found 1, refined 0, mBestTcw, the best
+ *   state's flags and count.  Otherwise found 0, n_inliers 0, all flags 0, Tcw all 0.
+ *   N < mRansacMinInliers (cc:210): no_more at once, no iteration.
+ *   CheckInliers (cc:381-418) keeps the reference's precision: Xc, Yc, invZc are the double
+ *   expressions rounded to float, ue / ve double, distX / distY the double differences rounded
+ *   to float, error2 = distX * distX + distY * distY in float with each operation rounded
+ *   (never fused), error2 < mvMaxError[i] strict; a NaN error2 is an outlier.
+ *   inliers / frame_mp [n] are written for the slots i < n only: frame_mp[i] = matches[i]
+ *   where inliers[i], else -1 (Tracking.cc:1600-1612), so orbx_pose_optimization_batch_device
+ *   can start from Tcw and frame_mp where they lie.  best_Tcw is mBestTcw (NaN before any best
+ *   state), best_iteration the absolute iteration that holds it (-1 if none), iterations =
+ *   mnIterations after the call, n_corr = N, min_inliers_used / max_its_used the adjusted
+ *   parameters, status the ORBX_PNP_STATUS_* bits.  Every output is a nullable device array
+ *   (host pointers to one candidate's for orbx_pnp_iterate). */
+typedef struct {
+    int32_t* found;             /* [B] */
+    int32_t* no_more;           /* [B] */
+    int32_t* n_inliers;         /* [B] */
+    uint8_t* inliers;           /* [B][cap] */
+    float* Tcw;                 /* [B][12] rows 0..2, as orbx_pose_optimization_batch.Tcw reads it */
+    int32_t* frame_mp;          /* [B][cap] */
+    float* best_Tcw;            /* [B][12] */
+    int32_t* best_inliers;      /* [B] */
+    int32_t* best_iteration;    /* [B] */
+    int32_t* refined;           /* [B] whether Tcw came from Refine() */
+    int32_t* iterations;        /* [B] */
+    int32_t* n_corr;            /* [B] */
+    int32_t* min_inliers_used;  /* [B] */
+    int32_t* max_its_used;      /* [B] */
+    int32_t* status;            /* [B] */
+} orbx_pnp_result;
+int orbx_pnp_iterate_device(orbx_pnp* s, int n_iterations, const orbx_pnp_result* out, void* stream);
+
+/* The single-candidate host forms: every pointer of the structs is a host pointer (batch 1;
+ * draws [n_draws][4] is copied).  orbx_pnp_set uploads once; orbx_pnp_iterate runs the batch
+ * kernels with B = 1, synchronises once and gives the same bytes as the batch form gives that
+ * candidate.  Its wall time is the matcher's orbx_matcher_last_call_us. */
+int orbx_pnp_set(orbx_pnp* s, const orbx_pnp_batch* in);
+int orbx_pnp_iterate(orbx_pnp* s, int n_iterations, const orbx_pnp_result* out);
+
+/* The reference's draws for n correspondences: draws [iterations][4], draw j =
+ * RandomInt(0, n - 1 - j) (DUtils/Random.cpp:47-49) over the C library's rand(); 0, without a
+ * rand() call, where n - j <= 0.  The same deviation as orbx_sim3_draws: the draws of all
+ * iterations are taken up front.  Host only, no GPU. */
+int orbx_pnp_draws(int32_t* draws, int n, int iterations);
+
 /* ---- Optimizer::OptimizeSim3: the Sim3 refinement of loop candidates ----
  * Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cc:
  * 1173-1358) as LoopClosing::ComputeSim3 calls it between SearchBySim3 and the nInliers >= 20

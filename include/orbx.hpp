@@ -721,6 +721,140 @@ private:
     float R_[9] = {}, t_[3] = {}, s_ = 0.0f;
 };
 
+// PnPsolver (include/PnPsolver.h, src/PnPsolver.cc:80-1345) on the arrays the adapter extracts
+// (INTEGRATION.md §4g): F.mvKeysUn, vpMapPointMatches as MapPoint ids into mpPos (GetWorldPos(),
+// 3 floats per id; -1 for NULL and isBad()), F.mvLevelSigma2 and fx fy cx cy.  draws: 4 per
+// iteration (empty: the reference's, from rand(), taken when SetRansacParameters runs: twice
+// maxIterations of them, since a call after the first runs beyond the cap, cc:226).  Runs on
+// the matcher's handle and stream; the matcher must outlive the solver.  iterate returns Tcw
+// (16 floats, row-major; empty: the reference's empty Mat).
+class PnPsolver {
+public:
+    PnPsolver(ORBmatcher& matcher, const std::vector<orbx_keypoint>& mvKeysUn,
+              const std::vector<int32_t>& vpMapPointMatches, const std::vector<float>& mpPos,
+              const std::vector<float>& mvLevelSigma2, const float* K, const std::vector<int32_t>& draws = {})
+        : m_(matcher.handle()), keys_(mvKeysUn), mp_(vpMapPointMatches), pos_(mpPos), sig_(mvLevelSigma2),
+          draws_(draws) {
+        n_ = (int)mp_.size();
+        if (keys_.size() < mp_.size()) throw Error(ORBX_ERR_ARG, "PnPsolver: one keypoint per slot of vpMapPointMatches");
+        for (int i = 0; i < 4; i++) K_[i] = K[i];
+        try {
+            SetRansacParameters();  // cc:127
+        } catch (...) {  // no destructor runs for a constructor that throws
+            orbx_pnp_destroy(h_);
+            throw;
+        }
+    }
+    ~PnPsolver() { orbx_pnp_destroy(h_); }
+    PnPsolver(const PnPsolver&) = delete;
+    PnPsolver& operator=(const PnPsolver&) = delete;
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4,
+                             float epsilon = 0.4f, float th2 = 5.991f) {
+        std::vector<int32_t> d(draws_);
+        if (d.empty()) {
+            int N = 0;
+            const int n_mp = (int)(pos_.size() / 3);
+            for (int i = 0; i < n_; i++) N += mp_[i] >= 0 && mp_[i] < n_mp;
+            d.resize((size_t)maxIterations * 8);
+            check(orbx_pnp_draws(d.data(), N, 2 * maxIterations));
+        }
+        const int nDraws = (int)(d.size() / 4);
+        if (!h_ || nDraws > maxDraws_) {
+            orbx_pnp_destroy(h_);
+            h_ = nullptr;
+            check(orbx_pnp_create(m_, 1, n_ > 0 ? n_ : 1, nDraws > 0 ? nDraws : 1, &h_));
+            maxDraws_ = nDraws;
+        }
+        orbx_pnp_batch in{};
+        const int32_t n = n_;
+        const int32_t none = -1;  // n == 0: the arrays are not read
+        const orbx_keypoint nokey{};
+        in.batch = 1;
+        in.cap = n_ > 0 ? n_ : 1;
+        in.kps = n_ ? keys_.data() : &nokey;
+        in.n = &n;
+        in.matches = n_ ? mp_.data() : &none;
+        in.n_mp = (int)(pos_.size() / 3);
+        in.mp_pos = pos_.data();
+        in.level_sigma2 = sig_.data();
+        in.nlevels = (int)sig_.size();
+        in.fx = K_[0];
+        in.fy = K_[1];
+        in.cx = K_[2];
+        in.cy = K_[3];
+        in.probability = probability;
+        in.min_inliers = minInliers;
+        in.max_iterations = maxIterations;
+        in.min_set = minSet;
+        in.epsilon = epsilon;
+        in.th2 = th2;
+        in.draws = d.data();
+        in.n_draws = nDraws;
+        check(orbx_pnp_set(h_, &in));
+        its_ = maxIterations;
+    }
+
+    std::vector<float> iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+        std::vector<uint8_t> inl((size_t)(n_ > 0 ? n_ : 1), 0);
+        frameMP.assign((size_t)(n_ > 0 ? n_ : 1), -1);
+        float T[12] = {};
+        int32_t found = 0, no_more = 0, n = 0;
+        orbx_pnp_result out{};
+        out.found = &found;
+        out.no_more = &no_more;
+        out.n_inliers = &n;
+        out.inliers = inl.data();
+        out.Tcw = T;
+        out.frame_mp = frameMP.data();
+        out.best_Tcw = bestTcw;
+        out.best_inliers = &bestInliers;
+        out.best_iteration = &bestIteration;
+        out.refined = &refined;
+        out.iterations = &iterations;
+        out.n_corr = &N;
+        out.min_inliers_used = &minInliersUsed;
+        out.max_its_used = &maxItsUsed;
+        out.status = &status;
+        check(orbx_pnp_iterate(h_, nIterations, &out));
+        frameMP.resize((size_t)n_);
+        bNoMore = no_more != 0;
+        nInliers = n;
+        vbInliers.assign((size_t)n_, false);
+        for (int i = 0; i < n_; i++) vbInliers[(size_t)i] = inl[(size_t)i] != 0;
+        std::vector<float> Tcw;
+        if (found) {
+            Tcw.assign(T, T + 12);
+            Tcw.insert(Tcw.end(), {0.0f, 0.0f, 0.0f, 1.0f});
+        }
+        return Tcw;
+    }
+    std::vector<float> find(std::vector<bool>& vbInliers, int& nInliers) {
+        bool bFlag;
+        return iterate(its_, bFlag, vbInliers, nInliers);  // cc:193-197
+    }
+    orbx_pnp* handle() { return h_; }
+
+    // after an iterate: mBestTcw (rows 0..2), mnBestInliers, the absolute iteration holding the
+    // best state (-1: none), whether the returned pose came from Refine(), mnIterations, N, the
+    // adjusted mRansacMinInliers / mRansacMaxIts, the ORBX_PNP_STATUS_* bits, and the frame's
+    // MapPoint ids with the outliers cleared (Tracking.cc:1600-1612)
+    float bestTcw[12] = {};
+    int32_t bestInliers = 0, bestIteration = -1, refined = 0, iterations = 0, N = 0, minInliersUsed = 0, maxItsUsed = 0,
+            status = 0;
+    std::vector<int32_t> frameMP;
+
+private:
+    orbx_matcher* m_;
+    orbx_pnp* h_ = nullptr;
+    std::vector<orbx_keypoint> keys_;
+    std::vector<int32_t> mp_;
+    std::vector<float> pos_, sig_;
+    std::vector<int32_t> draws_;
+    int n_ = 0, maxDraws_ = 0, its_ = 0;
+    float K_[4];
+};
+
 // Initializer (include/Initializer.h, src/Initializer.cc:64-1415) on the arrays the adapter
 // extracts: mvKeysUn of the reference frame at construction (Initializer(ReferenceFrame, sigma,
 // iterations), cc:43-56, with K as fx fy cx cy), mvKeysUn of the current frame and vMatches12 per

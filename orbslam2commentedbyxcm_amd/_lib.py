@@ -57,7 +57,8 @@ EXPORTED = [
     "orbx_kfdb_detect_loop_candidates_device", "orbx_kfdb_detect_relocalization_candidates",
     "orbx_kfdb_detect_loop_candidates", "orbx_pose_optimization_batch_device", "orbx_pose_optimization",
     "orbx_sim3_create", "orbx_sim3_destroy", "orbx_sim3_set_batch_device", "orbx_sim3_iterate_device", "orbx_sim3_set",
-    "orbx_sim3_iterate", "orbx_sim3_draws", "orbx_optimize_sim3_batch_device", "orbx_optimize_sim3",
+    "orbx_sim3_iterate", "orbx_sim3_draws", "orbx_pnp_create", "orbx_pnp_destroy", "orbx_pnp_set_batch_device",
+    "orbx_pnp_iterate_device", "orbx_pnp_set", "orbx_pnp_iterate", "orbx_pnp_draws", "orbx_optimize_sim3_batch_device", "orbx_optimize_sim3",
     "orbx_triangulate_pairs_batch_device", "orbx_triangulate_pairs",
     "orbx_local_bundle_adjustment_batch_device", "orbx_local_bundle_adjustment",
     "orbx_initializer_create", "orbx_initializer_destroy", "orbx_initializer_initialize_device",
@@ -149,6 +150,31 @@ class Sim3Result(C.Structure):
 
 ORBX_SIM3_MAX_ITERATIONS = 4096
 ORBX_SIM3_STATUS_BAD_DRAW = 1
+
+
+class PnpBatch(C.Structure):
+    """orbx_pnp_batch."""
+    _fields_ = [("batch", C.c_int), ("cap", C.c_int), ("kps", C.c_void_p), ("n", C.c_void_p), ("matches", C.c_void_p),
+                ("n_mp", C.c_int), ("mp_pos", C.c_void_p), ("level_sigma2", C.POINTER(C.c_float)),
+                ("nlevels", C.c_int), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("probability", C.c_double), ("min_inliers", C.c_int), ("max_iterations", C.c_int),
+                ("min_set", C.c_int), ("epsilon", C.c_float), ("th2", C.c_float), ("draws", C.c_void_p),
+                ("n_draws", C.c_int)]
+
+
+PNP_RESULT_FIELDS = ("found", "no_more", "n_inliers", "inliers", "Tcw", "frame_mp", "best_Tcw", "best_inliers",
+                     "best_iteration", "refined", "iterations", "n_corr", "min_inliers_used", "max_its_used",
+                     "status")
+
+
+class PnpResult(C.Structure):
+    """orbx_pnp_result."""
+    _fields_ = [(k, C.c_void_p) for k in PNP_RESULT_FIELDS]
+
+
+ORBX_PNP_MAX_DRAWS = 4096
+ORBX_PNP_STATUS_BAD_DRAW = 1
+ORBX_PNP_STATUS_NO_DRAWS = 2
 
 
 class OptimizeSim3Batch(C.Structure):
@@ -420,6 +446,14 @@ def lib() -> C.CDLL:
     L.orbx_sim3_set.argtypes = [vp, C.POINTER(Sim3Batch)]
     L.orbx_sim3_iterate.argtypes = [vp, C.c_int, C.POINTER(Sim3Result)]
     L.orbx_sim3_draws.argtypes = [i32p, C.c_int, C.c_int]
+    L.orbx_pnp_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.orbx_pnp_destroy.argtypes = [vp]
+    L.orbx_pnp_destroy.restype = None
+    L.orbx_pnp_set_batch_device.argtypes = [vp, C.POINTER(PnpBatch), vp]
+    L.orbx_pnp_iterate_device.argtypes = [vp, C.c_int, C.POINTER(PnpResult), vp]
+    L.orbx_pnp_set.argtypes = [vp, C.POINTER(PnpBatch)]
+    L.orbx_pnp_iterate.argtypes = [vp, C.c_int, C.POINTER(PnpResult)]
+    L.orbx_pnp_draws.argtypes = [i32p, C.c_int, C.c_int]
     L.orbx_optimize_sim3_batch_device.argtypes = [vp, C.POINTER(OptimizeSim3Batch), vp]
     L.orbx_optimize_sim3.argtypes = [vp, C.POINTER(OptimizeSim3Batch)]
     L.orbx_local_bundle_adjustment_batch_device.argtypes = [vp, C.POINTER(LocalBaBatch), vp]
