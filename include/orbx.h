@@ -1286,6 +1286,96 @@ int orbx_local_bundle_adjustment_batch_device(orbx_matcher* m, const orbx_local_
  * synchronisation; the same bytes as the batch form gives that problem. */
 int orbx_local_bundle_adjustment(orbx_matcher* m, const orbx_local_ba_batch* lba);
 
+/* ---- Optimizer::OptimizeEssentialGraph: batched Sim3 pose-graph Levenberg-Marquardt ----
+ * Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:873-1150) from the assembled graph to
+ * the recovered estimates, as LoopClosing::CorrectLoop calls it (LoopClosing.cc:621), with the
+ * g2o it runs (OptimizationAlgorithmLevenberg with setUserLambdaInit(1e-16) and optimize(20),
+ * BlockSolver_7_3 with nothing marginalised, VertexSim3Expmap, EdgeSim3 with information = I,
+ * no robust kernel and g2o's central-difference Jacobians, Sim3::log in full), for B maps in
+ * HBM in one launch: one persistent workgroup per problem.  Float inputs are widened to
+ * double, everything after is double, outputs are rounded to float once.  Every sum has one
+ * owner and a fixed shape (no floating-point atomics) and no workgroup waits on another: a
+ * problem's results are the same bytes whatever the batch around it.  The linear system is
+ * factored by a block-envelope (skyline) LDL^T without pivoting in natural (mnId) order that
+ * gives the bytes of the dense factorisation; only an exactly zero (or non-finite) pivot is
+ * a failed solve, which is a rejected trial.  There is no cap on keyframes.  DESIGN.md §4.22.
+ * Out of scope, with the caller: CorrectLoop's Sim3 propagation and first map-point
+ * correction (LoopClosing.cc:488-571), UpdateConnections, SearchAndFuse,
+ * UpdateNormalAndDepth, building the graph on the device, and global BA.
+ *   Problem b owns rows kf_off[b] .. kf_off[b + 1] of the keyframe table (the good keyframes
+ *   in ascending mnId), edge_off[b] .. of the edge table and pt_off[b] .. of the point table
+ *   (offsets over the whole tables, ascending).  kf_Tcw is the pose that gives the
+ *   non-corrected Sim3(Rcw, tcw, 1) of cc:994-1000 -- for a corrected keyframe the pose from
+ *   before CorrectLoop overwrote it (LoopClosing.cc:518-522).  The vertex estimate vScw is
+ *   corr_S[kf_corr[k]] (q xyzw, t, s: CorrectedSim3) where kf_corr[k] >= 0, the non-corrected
+ *   Sim3 otherwise.  loop_kf[b] (an index within the problem's rows) is fixed.
+ *   Edge e joins vertex 0 = edge_v[e][0] = i and vertex 1 = edge_v[e][1] = j (indices within
+ *   the problem's rows); its measurement is vScw[j] * vScw[i]^-1 for edge_kind 0 (the
+ *   LoopConnections edges, cc:954-986) and Snc[j] * Snc[i]^-1 for kind 1 (spanning tree, loop
+ *   and covisibility edges, cc:989-1089).  Edge order is the caller's, which is g2o's
+ *   insertion order (essential_graph_edges in the Python package writes it, with the
+ *   keyframes walked in ascending mnId); a pair may repeat, in either orientation.  An edge with an index outside the
+ *   rows, i == j or an unknown kind is no edge and sets ORBX_ESSENTIAL_GRAPH_STATUS_BAD_INDEX,
+ *   as does a kf_corr outside [-1, n_corr) (taken as -1) and a pt_ref outside the rows (the
+ *   point keeps its input bytes).  A keyframe without a valid edge keeps its estimate.
+ *   Outputs: kf_Tcw_opt = [R | t / s] of every keyframe's Sim3 (the fixed one's too, as in the
+ *   reference); pt_pos_opt = correctedSwr.map(Srw.map(P)) with r = pt_ref[p] (cc:1125-1142:
+ *   mnCorrectedReference where mnCorrectedByKF is the current keyframe, the reference keyframe
+ *   otherwise -- resolved by the caller); Scw_opt = the Sim3 estimates; trace = {LM
+ *   iterations, linear solves}; chi2 = {initial, final}; status = the
+ *   ORBX_ESSENTIAL_GRAPH_STATUS_* bits.  A problem whose loop_kf lies outside its rows
+ *   (NO_FIXED_KF), or whose envelope has more than max_env_blocks blocks (CAPACITY), returns
+ *   its inputs (Scw_opt = vScw) with a zero trace and chi2.  If no keyframe may move and has
+ *   an edge, no iteration runs.
+ *   iterations: 0 means the reference's 20.  dense != 0 forces the full envelope (first[f] =
+ *   0; a test switch: the same bytes, F (F + 1) / 2 blocks).
+ * Every pointer is a device pointer.  Scw_opt, trace and chi2 may be NULL.  Asynchronous on
+ * `stream` (or the matcher's). */
+#define ORBX_ESSENTIAL_GRAPH_STATUS_CAPACITY 1
+#define ORBX_ESSENTIAL_GRAPH_STATUS_NO_FIXED_KF 2
+#define ORBX_ESSENTIAL_GRAPH_STATUS_BAD_INDEX 4
+typedef struct {
+    int batch;
+    const int32_t* kf_off;           /* [B + 1] */
+    int n_kf;                        /* rows of the keyframe table */
+    const float* kf_Tcw;             /* [n_kf][12] rows 0..2 of the non-corrected pose */
+    const int32_t* kf_corr;          /* [n_kf] row of corr_S, or -1 */
+    const double* corr_S;            /* [n_corr][8] CorrectedSim3: q xyzw, t, s */
+    int n_corr;
+    const int32_t* loop_kf;          /* [B] */
+    const int32_t* edge_off;         /* [B + 1] */
+    int n_edges;
+    const int32_t* edge_v;           /* [n_edges][2] */
+    const int32_t* edge_kind;        /* [n_edges] */
+    const int32_t* pt_off;           /* [B + 1] */
+    int n_pt;
+    const float* pt_pos;             /* [n_pt][3] GetWorldPos() */
+    const int32_t* pt_ref;           /* [n_pt] */
+    int fix_scale;                   /* bFixScale */
+    int iterations;                  /* 0: 20 */
+    int64_t max_env_blocks;          /* 7 x 7 blocks per problem that the workspace is sized for
+                                        (orbx_essential_graph_envelope gives a problem's) */
+    int dense;                       /* test switch: the full envelope */
+    float* kf_Tcw_opt;               /* [n_kf][12] out */
+    float* pt_pos_opt;               /* [n_pt][3] out */
+    double* Scw_opt;                 /* [n_kf][8] out or NULL */
+    int32_t* trace;                  /* [B][2] out or NULL */
+    double* chi2;                    /* [B][2] out or NULL */
+    int32_t* status;                 /* [B] out */
+} orbx_essential_graph_batch;
+int orbx_optimize_essential_graph_batch_device(orbx_matcher* m, const orbx_essential_graph_batch* eg, void* stream);
+
+/* The single-problem host form: every pointer of the struct is a host pointer and batch is 1
+ * (kf_off = {0, n_kf}, edge_off = {0, n_edges}, pt_off = {0, n_pt}).  One upload, the batch
+ * kernel with B = 1, one synchronisation; the same bytes as the batch form gives that problem. */
+int orbx_optimize_essential_graph(orbx_matcher* m, const orbx_essential_graph_batch* eg);
+
+/* The blocks of one problem's envelope: over the keyframes other than `fixed` that have an
+ * edge (an edge here: both indices in [0, n_kf) and different -- the kinds are not looked at),
+ * indexed in order, sum of f - first[f] + 1 with first[f] the smallest index among f and its
+ * neighbours.  Host only, no GPU. */
+int orbx_essential_graph_envelope(int n_kf, int fixed, const int32_t* edge_v, int n_edges, int64_t* blocks);
+
 /* ---- LocalMapping::CreateNewMapPoints: triangulation and tests of the matched pairs ----
  * The second half of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:307-501) for the
  * vMatchedPairs that orbx_search_for_triangulation_batch_device left in HBM, with
@@ -1488,7 +1578,9 @@ int orbx_initializer_sets(int32_t* sets, int n, int iterations);
  * launch), "pz_byte" (byte-read k_pyramid), "desc_tiles" (tile-major describe),
  * "extract_dma" (single host call through DMA copies), "replay_threads" (64..1024),
  * "dup_stage" (launch extraction stage k twice), "oct_stamps" / "call_stamps" /
- * "match_stamps" (phase stamps to stderr).  value < 0 restores the default; name NULL
+ * "match_stamps" (phase stamps to stderr), "essgraph_stamps" (orbx_optimize_essential_graph*:
+ * problem 0's wall-clock ticks in the linearisations and in the linear solves to stderr;
+ * synchronises the stream).  value < 0 restores the default; name NULL
  * restores every default.  Every form gives the same results.  A frame size's plan reads
  * pz_seg / pz_byte / desc_tiles when an extractor first plans it. */
 int orbx_debug_set(const char* name, int value);

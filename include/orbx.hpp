@@ -397,6 +397,63 @@ public:
         if (status) *status = st;
         return n_erase;
     }
+
+    // OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3,
+    // LoopConnections, bFixScale) (src/Optimizer.cc:873-1150) from the assembled graph on: the
+    // good keyframes' non-corrected poses kfTcw (12 floats each, rows 0..2, ascending mnId),
+    // kfCorr (the keyframe's row of corrS, the CorrectedSim3 as q xyzw, t, s; -1: none), the
+    // row loopKF of pLoopKF, the edges (edgeV: vertex 0 and vertex 1 of each; edgeKind: 0 the
+    // LoopConnections edges, 1 the others) in g2o's insertion order, the map points mpPos (3
+    // floats each) and mpRef (the row of mnCorrectedReference or of the reference keyframe).
+    // kfTcw and mpPos are updated in place as SetPose / SetWorldPos do.  Scw (optional): the
+    // optimised Sim3 of every keyframe, 8 doubles each; trace (optional, 2 ints): the LM
+    // iterations run and the linear solves tried; chi2 (optional, 2 doubles): initial and
+    // final.  Returns the ORBX_ESSENTIAL_GRAPH_STATUS_* bits.
+    static int OptimizeEssentialGraph(ORBmatcher& matcher, std::vector<float>& kfTcw, const std::vector<int32_t>& kfCorr,
+                                      const std::vector<double>& corrS, int loopKF, const std::vector<int32_t>& edgeV,
+                                      const std::vector<int32_t>& edgeKind, std::vector<float>& mpPos,
+                                      const std::vector<int32_t>& mpRef, bool bFixScale,
+                                      std::vector<double>* Scw = nullptr, int32_t* trace = nullptr,
+                                      double* chi2 = nullptr, int iterations = 0) {
+        const int32_t nkf = (int32_t)kfCorr.size(), ne = (int32_t)edgeKind.size(), npt = (int32_t)mpRef.size();
+        if (kfTcw.size() != (size_t)nkf * 12 || corrS.size() % 8 || edgeV.size() != (size_t)ne * 2 ||
+            mpPos.size() != (size_t)npt * 3)
+            throw std::runtime_error("OptimizeEssentialGraph: array sizes differ");
+        const int32_t kf_off[2] = {0, nkf}, edge_off[2] = {0, ne}, pt_off[2] = {0, npt}, loop = loopKF;
+        std::vector<float> Tout(kfTcw.size()), Xout(mpPos.size());
+        if (Scw) Scw->assign((size_t)nkf * 8, 0.0);
+        int32_t st = 0;
+        orbx_essential_graph_batch q{};
+        check(orbx_essential_graph_envelope(nkf, loopKF, edgeV.data(), ne, &q.max_env_blocks));
+        q.batch = 1;
+        q.kf_off = kf_off;
+        q.n_kf = nkf;
+        q.kf_Tcw = kfTcw.data();
+        q.kf_corr = kfCorr.data();
+        q.corr_S = corrS.data();
+        q.n_corr = (int)(corrS.size() / 8);
+        q.loop_kf = &loop;
+        q.edge_off = edge_off;
+        q.n_edges = ne;
+        q.edge_v = edgeV.data();
+        q.edge_kind = edgeKind.data();
+        q.pt_off = pt_off;
+        q.n_pt = npt;
+        q.pt_pos = mpPos.data();
+        q.pt_ref = mpRef.data();
+        q.fix_scale = bFixScale ? 1 : 0;
+        q.iterations = iterations;
+        q.kf_Tcw_opt = Tout.data();
+        q.pt_pos_opt = Xout.data();
+        q.Scw_opt = Scw ? Scw->data() : nullptr;
+        q.trace = trace;
+        q.chi2 = chi2;
+        q.status = &st;
+        check(orbx_optimize_essential_graph(matcher.handle(), &q));
+        kfTcw = Tout;
+        mpPos = Xout;
+        return st;
+    }
 };
 
 // LocalMapping::CreateNewMapPoints' triangulation and tests (src/LocalMapping.cc:307-501) for one

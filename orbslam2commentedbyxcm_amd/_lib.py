@@ -61,6 +61,7 @@ EXPORTED = [
     "orbx_pnp_iterate_device", "orbx_pnp_set", "orbx_pnp_iterate", "orbx_pnp_draws", "orbx_optimize_sim3_batch_device", "orbx_optimize_sim3",
     "orbx_triangulate_pairs_batch_device", "orbx_triangulate_pairs",
     "orbx_local_bundle_adjustment_batch_device", "orbx_local_bundle_adjustment",
+    "orbx_optimize_essential_graph_batch_device", "orbx_optimize_essential_graph", "orbx_essential_graph_envelope",
     "orbx_initializer_create", "orbx_initializer_destroy", "orbx_initializer_initialize_device",
     "orbx_initializer_initialize", "orbx_initializer_sets",
 ]
@@ -206,6 +207,22 @@ ORBX_LOCAL_BA_MAX_FREE_KF = 64
 ORBX_LOCAL_BA_STATUS_CAPACITY = 1
 ORBX_LOCAL_BA_STATUS_NO_FREE_KF = 2
 ORBX_LOCAL_BA_STATUS_BAD_INDEX = 4
+
+
+class EssentialGraphBatch(C.Structure):
+    """orbx_essential_graph_batch."""
+    _fields_ = [("batch", C.c_int), ("kf_off", C.c_void_p), ("n_kf", C.c_int), ("kf_Tcw", C.c_void_p),
+                ("kf_corr", C.c_void_p), ("corr_S", C.c_void_p), ("n_corr", C.c_int), ("loop_kf", C.c_void_p),
+                ("edge_off", C.c_void_p), ("n_edges", C.c_int), ("edge_v", C.c_void_p), ("edge_kind", C.c_void_p),
+                ("pt_off", C.c_void_p), ("n_pt", C.c_int), ("pt_pos", C.c_void_p), ("pt_ref", C.c_void_p),
+                ("fix_scale", C.c_int), ("iterations", C.c_int), ("max_env_blocks", C.c_int64), ("dense", C.c_int),
+                ("kf_Tcw_opt", C.c_void_p), ("pt_pos_opt", C.c_void_p), ("Scw_opt", C.c_void_p), ("trace", C.c_void_p),
+                ("chi2", C.c_void_p), ("status", C.c_void_p)]
+
+
+ORBX_ESSENTIAL_GRAPH_STATUS_CAPACITY = 1
+ORBX_ESSENTIAL_GRAPH_STATUS_NO_FIXED_KF = 2
+ORBX_ESSENTIAL_GRAPH_STATUS_BAD_INDEX = 4
 
 
 class KeyFrameGeomDevice(C.Structure):
@@ -458,6 +475,9 @@ def lib() -> C.CDLL:
     L.orbx_optimize_sim3.argtypes = [vp, C.POINTER(OptimizeSim3Batch)]
     L.orbx_local_bundle_adjustment_batch_device.argtypes = [vp, C.POINTER(LocalBaBatch), vp]
     L.orbx_local_bundle_adjustment.argtypes = [vp, C.POINTER(LocalBaBatch)]
+    L.orbx_optimize_essential_graph_batch_device.argtypes = [vp, C.POINTER(EssentialGraphBatch), vp]
+    L.orbx_optimize_essential_graph.argtypes = [vp, C.POINTER(EssentialGraphBatch)]
+    L.orbx_essential_graph_envelope.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_int64)]
     L.orbx_triangulate_pairs_batch_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, i32p, C.c_int, vp, vp, C.c_float,
                                                       C.c_float, C.POINTER(NewMapPoints), vp]
     L.orbx_triangulate_pairs.argtypes = [vp, C.POINTER(KeyFrameGeomDevice), C.POINTER(KeyFrameGeomDevice), vp, C.c_int,

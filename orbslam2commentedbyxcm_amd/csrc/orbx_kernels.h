@@ -233,6 +233,57 @@ struct LocalBaArgs {
 size_t local_ba_workspace_bytes(int batch, int n_kf, int n_pt, int n_obs, int max_free);
 hipError_t launch_local_ba(LocalBaArgs A, int batch, char* workspace, hipStream_t stream);
 
+// k_essential_graph (orbx_essgraph.hip): Optimizer::OptimizeEssentialGraph for `batch` maps,
+// one workgroup each; the estimates, the measurements, the Jacobians, the block envelope of H,
+// its factor and every vector live in the workspace.
+struct EssGraphArgs {
+    const int32_t* kf_off;       // [B + 1]
+    int n_kf;
+    const float* kf_Tcw;         // [n_kf][12]
+    const int32_t* kf_corr;      // [n_kf] row of corr_S or -1
+    const double* corr_S;        // [n_corr][8]
+    int n_corr;
+    const int32_t* loop_kf;      // [B]
+    const int32_t* edge_off;     // [B + 1]
+    int n_edges;
+    const int32_t* edge_v;       // [n_edges][2]
+    const int32_t* edge_kind;    // [n_edges]
+    const int32_t* pt_off;       // [B + 1]
+    int n_pt;
+    const float* pt_pos;         // [n_pt][3]
+    const int32_t* pt_ref;       // [n_pt]
+    int fix_scale, iterations, dense;
+    long long max_env_blocks;    // blocks per problem that H and its factor are sized for
+    float* kf_Tcw_out;           // [n_kf][12]
+    float* pt_pos_out;           // [n_pt][3]
+    double* Scw_out;             // [n_kf][8] or null
+    int32_t* trace;              // [B][2] or null
+    double* chi2;                // [B][2] or null
+    int32_t* status;             // [B]
+    // set by launch_essential_graph
+    long long* ticks;            // [B][2] wall-clock ticks {linearisations, solves}; null unless "essgraph_stamps"
+    double probes[14 * 8];       // Sim3(+-1e-9 e_d) as q xyzw, t, s
+    double* S;                   // [n_kf][3][8]: vScw, the estimate, its backup
+    double* meas;                // [n_edges][8]
+    double* J;                   // [n_edges][2][49]
+    double* err;                 // [n_edges][7]
+    double* H;                   // [B][max_env_blocks][49]
+    double* L;                   // [B][max_env_blocks][49]
+    double* vec;                 // [n_kf][4][7]: b, x, and the two work vectors of the solve
+    long long* col_off;          // [n_kf + B] first block of a column (F + 1 per problem)
+    long long* row_off;          // [n_kf + B] first entry of a block row in rows
+    int32_t* rows;               // [B][max_env_blocks] the columns of every block row
+    int32_t* edge_ok;            // [n_edges]
+    int32_t* free_idx;           // [n_kf] index among the vertices that may move, -1: none
+    int32_t* free_kf;            // [n_kf] its inverse
+    int32_t* first;              // [n_kf + B]
+    int32_t* adj_off;            // [n_kf + B]
+    int32_t* adj;                // [n_edges][2]: 2 e + side, per vertex in edge order
+    int32_t* deg;                // [n_kf]
+};
+size_t essential_graph_workspace_bytes(int batch, int n_kf, int n_edges, long long max_env_blocks);
+hipError_t launch_essential_graph(EssGraphArgs A, int batch, char* workspace, hipStream_t stream);
+
 // k_triangulate_pairs (orbx_triangulate.hip): LocalMapping::CreateNewMapPoints' triangulation
 // and tests (LocalMapping.cc:307-501) over the matched pairs of `npairs` keyframe pairs, one
 // workgroup each.

@@ -2307,6 +2307,137 @@ int orbx_local_bundle_adjustment(orbx_matcher* m, const orbx_local_ba_batch* q) 
     return ORBX_OK;
 }
 
+static const char* essential_graph_check(const orbx_essential_graph_batch* q) {
+    if (q->batch < 0 || q->n_kf < 0 || q->n_corr < 0 || q->n_edges < 0 || q->n_pt < 0 || q->iterations < 0 ||
+        q->max_env_blocks < 0)
+        return "bad argument";
+    if (q->batch == 0) return nullptr;
+    if (!q->kf_off || !q->edge_off || !q->pt_off || !q->loop_kf || !q->status) return "null buffer";
+    if (q->n_kf > 0 && (!q->kf_Tcw || !q->kf_corr || !q->kf_Tcw_opt)) return "null keyframe table";
+    if (q->n_corr > 0 && !q->corr_S) return "null corrected table";
+    if (q->n_edges > 0 && (!q->edge_v || !q->edge_kind)) return "null edge table";
+    if (q->n_pt > 0 && (!q->pt_pos || !q->pt_ref || !q->pt_pos_opt)) return "null point table";
+    if (q->n_kf >= (1 << 24) || q->n_edges >= (1 << 26) || q->n_pt >= (1 << 26)) return "table too large";
+    if (q->max_env_blocks >= ((int64_t)1 << 31) / q->batch) return "batch x max_env_blocks of 2^31 or more";
+    return nullptr;
+}
+
+// host offsets {0, n}: ascending by construction; the batch form's live in HBM and are clamped
+// by the kernel
+static bool spans(const int32_t* off, int n) { return off[0] == 0 && off[1] == n; }
+
+// Optimizer::OptimizeEssentialGraph for a batch of maps in HBM (see include/orbx.h)
+int orbx_optimize_essential_graph_batch_device(orbx_matcher* m, const orbx_essential_graph_batch* q, void* stream) {
+    if (!m || !q) return fail(ORBX_ERR_ARG, "null argument");
+    if (const char* why = essential_graph_check(q)) return fail(ORBX_ERR_ARG, why);
+    const int B = q->batch;
+    if (B == 0) return ORBX_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+    HIP_TRY(m->pscr.reserve(essential_graph_workspace_bytes(B, q->n_kf, q->n_edges, q->max_env_blocks), s));
+    EssGraphArgs A{};
+    A.kf_off = q->kf_off;
+    A.n_kf = q->n_kf;
+    A.kf_Tcw = q->kf_Tcw;
+    A.kf_corr = q->kf_corr;
+    A.corr_S = q->corr_S;
+    A.n_corr = q->n_corr;
+    A.loop_kf = q->loop_kf;
+    A.edge_off = q->edge_off;
+    A.n_edges = q->n_edges;
+    A.edge_v = q->edge_v;
+    A.edge_kind = q->edge_kind;
+    A.pt_off = q->pt_off;
+    A.n_pt = q->n_pt;
+    A.pt_pos = q->pt_pos;
+    A.pt_ref = q->pt_ref;
+    A.fix_scale = q->fix_scale;
+    A.iterations = q->iterations;
+    A.dense = q->dense;
+    A.max_env_blocks = q->max_env_blocks;
+    A.kf_Tcw_out = q->kf_Tcw_opt;
+    A.pt_pos_out = q->pt_pos_opt;
+    A.Scw_out = q->Scw_opt;
+    A.trace = q->trace;
+    A.chi2 = q->chi2;
+    A.status = q->status;
+    HIP_TRY(launch_essential_graph(A, B, m->pscr.p, s));
+    return ORBX_OK;
+}
+
+// The single-problem host form: one staged problem, the batch kernel, one synchronisation.
+int orbx_optimize_essential_graph(orbx_matcher* m, const orbx_essential_graph_batch* q) {
+    if (!m || !q) return fail(ORBX_ERR_ARG, "null argument");
+    if (q->batch != 1) return fail(ORBX_ERR_ARG, "the host form takes one problem");
+    if (const char* why = essential_graph_check(q)) return fail(ORBX_ERR_ARG, why);
+    if (!spans(q->kf_off, q->n_kf) || !spans(q->edge_off, q->n_edges) || !spans(q->pt_off, q->n_pt))
+        return fail(ORBX_ERR_ARG, "the host form's offsets are {0, n_kf}, {0, n_edges} and {0, n_pt}");
+    CallClock clock(m);
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    const size_t nk = (size_t)q->n_kf, ne = (size_t)q->n_edges, np = (size_t)q->n_pt, nc = (size_t)q->n_corr;
+    const size_t ck = nk ? nk : 1, ce = ne ? ne : 1, cp = np ? np : 1, cc = nc ? nc : 1;
+    struct {
+        int32_t kf_off[2], edge_off[2], pt_off[2], loop_kf, spare;
+    } in{{0, q->n_kf}, {0, q->n_edges}, {0, q->n_pt}, q->loop_kf[0], 0}, *d_in = nullptr;
+    orbx_essential_graph_batch d = *q;
+    HostStage st(pad);
+    st.out(&d.status, &q->status, 1, 1);
+    st.out(&d.trace, &q->trace, 2, 2);
+    st.out(&d.chi2, &q->chi2, 2, 2);
+    st.out(&d.kf_Tcw_opt, &q->kf_Tcw_opt, 12 * nk, 12 * ck);
+    st.out(&d.pt_pos_opt, &q->pt_pos_opt, 3 * np, 3 * cp);
+    st.out(&d.Scw_opt, &q->Scw_opt, 8 * nk, 8 * ck);
+    st.in(&d.kf_Tcw, q->kf_Tcw, 12 * nk, 12 * ck);
+    st.in(&d.kf_corr, q->kf_corr, nk, ck);
+    st.in(&d.corr_S, q->corr_S, 8 * nc, 8 * cc);
+    st.in(&d.edge_v, q->edge_v, 2 * ne, 2 * ce);
+    st.in(&d.edge_kind, q->edge_kind, ne, ce);
+    st.in(&d.pt_pos, q->pt_pos, 3 * np, 3 * cp);
+    st.in(&d.pt_ref, q->pt_ref, np, cp);
+    st.in(&d_in, &in, 1, 1);
+    HIP_TRY(st.stage(m->pstage, s));
+    d.kf_off = d_in->kf_off;
+    d.edge_off = d_in->edge_off;
+    d.pt_off = d_in->pt_off;
+    d.loop_kf = &d_in->loop_kf;
+    const int rc = orbx_optimize_essential_graph_batch_device(m, &d, s);
+    if (rc) return rc;
+    HIP_TRY(st.download(s));
+    return ORBX_OK;
+}
+
+// A problem's envelope blocks (see include/orbx.h)
+int orbx_essential_graph_envelope(int n_kf, int fixed, const int32_t* edge_v, int n_edges, int64_t* blocks) {
+    if (n_kf < 0 || n_edges < 0 || !blocks || (n_edges > 0 && !edge_v)) return fail(ORBX_ERR_ARG, "bad argument");
+    auto edge = [&](int e, int& i, int& j) {
+        i = edge_v[2 * e];
+        j = edge_v[2 * e + 1];
+        return i >= 0 && i < n_kf && j >= 0 && j < n_kf && i != j;
+    };
+    std::vector<int32_t> idx((size_t)n_kf, -1), first;
+    std::vector<char> has((size_t)n_kf, 0);
+    int i, j;
+    for (int e = 0; e < n_edges; e++)
+        if (edge(e, i, j)) has[(size_t)i] = has[(size_t)j] = 1;
+    int F = 0;
+    for (int v = 0; v < n_kf; v++)
+        if (v != fixed && has[(size_t)v]) idx[(size_t)v] = F++;
+    first.resize((size_t)F);
+    for (int f = 0; f < F; f++) first[(size_t)f] = f;
+    for (int e = 0; e < n_edges; e++) {
+        if (!edge(e, i, j)) continue;
+        const int a = idx[(size_t)i], b = idx[(size_t)j];
+        if (a < 0 || b < 0) continue;
+        int32_t& fm = first[(size_t)std::max(a, b)];
+        fm = std::min<int32_t>(fm, std::min(a, b));
+    }
+    int64_t n = 0;
+    for (int f = 0; f < F; f++) n += f - first[(size_t)f] + 1;
+    *blocks = n;
+    return ORBX_OK;
+}
+
 static const char* triangulate_check(int nkf, const orbx_keyframe_geom_device* kfs, const orbx_frame_view* cam,
                                      int npairs, const int32_t* pairs, int cap, const int32_t* d_pairs,
                                      const int32_t* d_npairs, const orbx_new_mappoints* out) {

@@ -41,6 +41,7 @@
 #include "orbx.h"
 #include "orbx_kernels.h"
 #include "orbx_lm.h"
+#include "orbx_sim3.h"
 
 namespace orbx {
 
@@ -51,136 +52,6 @@ constexpr int kOsWaves = kOsThreads / 64;
 constexpr int kOsSums = 36;      // H upper [28], -b [7], chi
 constexpr int kOsRecWords = 12;  // P3D1c[3], P3D2c[3], obs1[2], obs2[2], invSigma2 of either keyframe
 constexpr int kOsXf = 15;        // transforms per direction: 14 probes and the estimate
-
-struct S3 {
-    double qx, qy, qz, qw, tx, ty, tz, s;
-};
-
-// Sim3::operator*, sim3.h:266-272
-__host__ __device__ __forceinline__ S3 s3_mul(const S3& a, const S3& b) {
-    S3 o;
-    o.qx = a.qw * b.qx + a.qx * b.qw + a.qy * b.qz - a.qz * b.qy;
-    o.qy = a.qw * b.qy + a.qy * b.qw + a.qz * b.qx - a.qx * b.qz;
-    o.qz = a.qw * b.qz + a.qz * b.qw + a.qx * b.qy - a.qy * b.qx;
-    o.qw = a.qw * b.qw - a.qx * b.qx - a.qy * b.qy - a.qz * b.qz;
-    double ux = a.qy * b.tz - a.qz * b.ty, uy = a.qz * b.tx - a.qx * b.tz, uz = a.qx * b.ty - a.qy * b.tx;
-    ux += ux;
-    uy += uy;
-    uz += uz;
-    const double rx = b.tx + a.qw * ux + (a.qy * uz - a.qz * uy);
-    const double ry = b.ty + a.qw * uy + (a.qz * ux - a.qx * uz);
-    const double rz = b.tz + a.qw * uz + (a.qx * uy - a.qy * ux);
-    o.tx = a.s * rx + a.tx;
-    o.ty = a.s * ry + a.ty;
-    o.tz = a.s * rz + a.tz;
-    o.s = a.s * b.s;
-    return o;
-}
-
-// Sim3::inverse, sim3.h:233-236
-__device__ __forceinline__ S3 s3_inverse(const S3& a) {
-    S3 o;
-    o.qx = -a.qx;
-    o.qy = -a.qy;
-    o.qz = -a.qz;
-    o.qw = a.qw;
-    const double k = -1. / a.s;
-    lm::quat_rotate(o.qx, o.qy, o.qz, o.qw, k * a.tx, k * a.ty, k * a.tz, o.tx, o.ty, o.tz);
-    o.s = 1. / a.s;
-    return o;
-}
-
-// Sim3(const Vector7d& update), sim3.h:70-142: update = (omega, upsilon, sigma)
-__host__ __device__ __forceinline__ S3 s3_exp(const double (&x)[7]) {
-    const double w0 = x[0], w1 = x[1], w2 = x[2], sigma = x[6];
-    const double theta = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
-    const double O[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
-    const double s = exp(sigma);
-    double O2[3][3], R[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) O2[i][j] = O[i][0] * O[0][j] + O[i][1] * O[1][j] + O[i][2] * O[2][j];
-    const double eps = 0.00001;
-    double A, B, C;
-    const bool small_theta = theta < eps;
-    double ra = 1.0, rb = 1.0;  // R = I + ra Omega + rb Omega2
-    if (!small_theta) {
-        ra = sin(theta) / theta;
-        rb = (1 - cos(theta)) / (theta * theta);
-    }
-    if (fabs(sigma) < eps) {
-        C = 1;
-        if (small_theta) {
-            A = 1. / 2.;
-            B = 1. / 6.;
-        } else {
-            const double theta2 = theta * theta;
-            A = (1 - cos(theta)) / (theta2);
-            B = (theta - sin(theta)) / (theta2 * theta);
-        }
-    } else {
-        C = (s - 1) / sigma;
-        if (small_theta) {
-            const double sigma2 = sigma * sigma;
-            A = ((sigma - 1) * s + 1) / sigma2;
-            B = ((0.5 * sigma2 - sigma + 1) * s) / (sigma2 * sigma);
-        } else {
-            const double a = s * sin(theta);
-            const double b = s * cos(theta);
-            const double theta2 = theta * theta;
-            const double sigma2 = sigma * sigma;
-            const double c = theta2 + sigma2;
-            A = (a * sigma + (1 - b) * theta) / (theta * c);
-            B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
-        }
-    }
-    double W[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            const double id = i == j ? 1.0 : 0.0;
-            R[i][j] = small_theta ? id + O[i][j] + O2[i][j] : id + ra * O[i][j] + rb * O2[i][j];
-            W[i][j] = A * O[i][j] + B * O2[i][j] + C * id;
-        }
-    double q[4];
-    lm::quat_from_matrix(R, q);
-    S3 o;
-    o.qx = q[0];
-    o.qy = q[1];
-    o.qz = q[2];
-    o.qw = q[3];
-    o.tx = W[0][0] * x[3] + W[0][1] * x[4] + W[0][2] * x[5];
-    o.ty = W[1][0] * x[3] + W[1][1] * x[4] + W[1][2] * x[5];
-    o.tz = W[2][0] * x[3] + W[2][1] * x[4] + W[2][2] * x[5];
-    o.s = s;
-    return o;
-}
-
-__device__ __forceinline__ S3 s3_load(const double* p) {
-    S3 o;
-    o.qx = p[0];
-    o.qy = p[1];
-    o.qz = p[2];
-    o.qw = p[3];
-    o.tx = p[4];
-    o.ty = p[5];
-    o.tz = p[6];
-    o.s = p[7];
-    return o;
-}
-
-__device__ __forceinline__ void s3_store(double* p, const S3& a) {
-    p[0] = a.qx;
-    p[1] = a.qy;
-    p[2] = a.qz;
-    p[3] = a.qw;
-    p[4] = a.tx;
-    p[5] = a.ty;
-    p[6] = a.tz;
-    p[7] = a.s;
-}
 
 struct Cam2 {
     double fx, fy, cx, cy;
@@ -572,18 +443,7 @@ hipError_t launch_opt_sim3(OptSim3Args A, int batch, char* workspace, hipStream_
     A.rec = (float*)workspace;
     A.eidx = (int32_t*)(workspace + rows * kOsRecWords * 4);
     A.active = A.eidx + rows;
-    // The probe increments Sim3(+-1e-9 e_d) of g2o's central difference, by the host's libm;
-    // with fix_scale oplusImpl zeroes the seventh entry, so both of its probes are Sim3(0)
-    static_assert(sizeof(S3) == 8 * sizeof(double), "probe layout");
-    for (int d = 0; d < 7; d++)
-        for (int sgn = 0; sgn < 2; sgn++) {
-            double x[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            x[d] = sgn ? -1e-9 : 1e-9;
-            if (A.fix_scale) x[6] = 0;
-            const S3 p = s3_exp(x);
-            const double v[8] = {p.qx, p.qy, p.qz, p.qw, p.tx, p.ty, p.tz, p.s};
-            for (int k = 0; k < 8; k++) A.probes[(2 * d + sgn) * 8 + k] = v[k];
-        }
+    s3_probe_increments(A.fix_scale != 0, A.probes);
     k_opt_sim3<<<batch, kOsThreads, 0, stream>>>(A);
     return hipGetLastError();
 }

@@ -41,6 +41,7 @@ constexpr Knob kKnobs[] = {
     {"oct_stamps", "ORBX_OCT_STAMPS"},         // k_octree phase stamps (diagnostics)
     {"call_stamps", "ORBX_CALL_STAMPS"},       // single matcher calls' phase stamps (diagnostics)
     {"match_stamps", "ORBX_MATCH_STAMPS"},     // batched matcher phase stamps (diagnostics)
+    {"essgraph_stamps", "ORBX_ESSGRAPH_STAMPS"},  // k_essential_graph's linearisation / solve ticks (diagnostics)
 };
 constexpr int kNumKnobs = sizeof(kKnobs) / sizeof(kKnobs[0]);
 std::atomic<int> g_set[kNumKnobs];      // orbx_debug_set values

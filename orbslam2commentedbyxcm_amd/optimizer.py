@@ -1,5 +1,6 @@
-"""Optimizer::PoseOptimization, Optimizer::OptimizeSim3 and Optimizer::LocalBundleAdjustment on
-the GPU (include/orbx.h, csrc/orbx_poseopt.hip, csrc/orbx_optsim3.hip, csrc/orbx_localba.hip).
+"""Optimizer::PoseOptimization, Optimizer::OptimizeSim3, Optimizer::LocalBundleAdjustment and
+Optimizer::OptimizeEssentialGraph on the GPU (include/orbx.h, csrc/orbx_poseopt.hip,
+csrc/orbx_optsim3.hip, csrc/orbx_localba.hip, csrc/orbx_essgraph.hip).
 
 PoseOptimizer mirrors the one g2o call on ORB-SLAM2's per-frame path
 (src/Optimizer.cc:299-502): PoseOptimization for one frame on host arrays, and
@@ -8,7 +9,10 @@ pose_optimization_batch_device for B frames in HBM with the callers' epilogue
 (src/Optimizer.cc:1173-1358): OptimizeSim3 for one loop candidate on host arrays, and
 optimize_sim3_batch_device for B candidates in HBM.  LocalBundleAdjuster mirrors the one of
 LocalMapping::Run (src/Optimizer.cc:586-853): LocalBundleAdjustment for one local map on host
-arrays, and local_ba_batch_device for B local maps in HBM.
+arrays, and local_ba_batch_device for B local maps in HBM.  EssentialGraphOptimizer mirrors the
+one of LoopClosing::CorrectLoop (src/Optimizer.cc:873-1150): OptimizeEssentialGraph for one map
+on host arrays, and essential_graph_batch_device for B maps in HBM; essential_graph_edges
+writes the graph's edges in the reference's order on the host.
 """
 from __future__ import annotations
 
@@ -354,3 +358,129 @@ class LocalBundleAdjuster(PoseOptimizer):
         q.n_erase, q.trace, q.status = ptr(d_n_erase), ptr(d_trace), ptr(d_status)
         s = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
         L.check(L.lib().orbx_local_bundle_adjustment_batch_device(self._h, C.byref(q), s))
+
+
+def essential_graph_envelope(n_kf: int, fixed: int, edge_v) -> int:
+    """orbx_essential_graph_envelope: the 7 x 7 blocks of one problem's envelope (max_env_blocks)."""
+    ev = np.ascontiguousarray(edge_v, dtype=np.int32).reshape(-1, 2)
+    n = C.c_int64(0)
+    L.check(L.lib().orbx_essential_graph_envelope(int(n_kf), int(fixed), C.c_void_p(ev.ctypes.data), len(ev),
+                                                  C.byref(n)))
+    return int(n.value)
+
+
+def essential_graph_edges(ids, parent, children, loop_edges, covisibles, loop_connections, cur_id, loop_id,
+                          min_feat: int = 100):
+    """The edges of Optimizer::OptimizeEssentialGraph as src/Optimizer.cc:954-1089 inserts them, on
+    the host, with the keyframes walked in ascending mnId.  ids: the mnId of the good keyframes, ascending (row
+    k of the tables is keyframe ids[k]); parent[k]: the mnId of GetParent() or -1; children[k]:
+    the mnIds of its children (hasChild); loop_edges[k]: the mnIds of GetLoopEdges(), in the
+    set's order; covisibles[k]: (mnId, weight) pairs in GetCovisiblesByWeight order -- every
+    connected keyframe, the weights decide (a keyframe that is not in ids is bad and is skipped);
+    loop_connections: an ORDERED list of (mnId, [(mnId, weight), ...]) -- the reference iterates a
+    map<KeyFrame*, set<KeyFrame*>>, whose order is pointer order, so the order is taken as given,
+    as is the order within each set.  The reference's walk over the keyframes (cc:989) is pointer
+    order too (GetAllKeyFrames() copies a set<KeyFrame*>); here the keyframes are walked in
+    ascending mnId, by choice: the order of `ids`.  Returns edge_v (E, 2) i32 (row indices: vertex 0, vertex 1)
+    and edge_kind (E,) i32 (0: LoopConnections, 1: spanning tree, loop and covisibility edges)."""
+    row = {int(m): k for k, m in enumerate(ids)}
+    ev, kind, inserted = [], [], set()
+    for mi, conns in loop_connections:                       # cc:954-986
+        for mj, w in conns:
+            if (mi != cur_id or mj != loop_id) and w < min_feat:
+                continue
+            ev.append((row[int(mi)], row[int(mj)]))
+            kind.append(0)
+            inserted.add((min(mi, mj), max(mi, mj)))
+    for k, mi in enumerate(ids):                             # cc:989-1089
+        par = int(parent[k])
+        if par >= 0:
+            ev.append((k, row[par]))
+            kind.append(1)
+        loops = [int(m) for m in loop_edges[k]]
+        for ml in loops:
+            if ml < mi:
+                ev.append((k, row[ml]))
+                kind.append(1)
+        kids = set(int(m) for m in children[k])
+        for mn, w in covisibles[k]:
+            mn = int(mn)
+            if w < min_feat or mn == par or mn in kids or mn in loops:
+                continue
+            if mn not in row or not mn < mi:
+                continue
+            if (min(mi, mn), max(mi, mn)) in inserted:
+                continue
+            ev.append((k, row[mn]))
+            kind.append(1)
+    return np.array(ev, np.int32).reshape(-1, 2), np.array(kind, np.int32)
+
+
+class EssentialGraphOptimizer(PoseOptimizer):
+    """Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:873-1150) on the GPU
+    (csrc/orbx_essgraph.hip): OptimizeEssentialGraph for one map on host arrays and
+    essential_graph_batch_device for B maps in HBM.  CorrectLoop's Sim3 propagation, the graph's
+    assembly (essential_graph_edges) and the updates after it stay with the caller.  The handle,
+    close() and last_call_us() are PoseOptimizer's."""
+
+    def OptimizeEssentialGraph(self, kf_Tcw, kf_corr, corr_S, loop_kf, edge_v, edge_kind, pt_pos, pt_ref,
+                               fix_scale: bool, iterations: int = 0, max_env_blocks: int | None = None,
+                               dense: bool = False) -> dict:
+        """One map on host arrays: kf_Tcw (K, 12) f32 (the non-corrected poses, ascending mnId),
+        kf_corr (K,) rows of corr_S or -1, corr_S (n_corr, 8) f64 (q xyzw, t, s), loop_kf the
+        fixed keyframe's row, edge_v (E, 2) / edge_kind (E,), pt_pos (P, 3) f32, pt_ref (P,).
+        max_env_blocks None: what the problem needs.  Returns Tcw (K, 12) and pos (P, 3) f32,
+        Scw (K, 8) f64, trace (2,) i32, chi2 (2,) f64 and status."""
+        T = _f32(kf_Tcw).reshape(-1, 12)
+        corr = np.ascontiguousarray(kf_corr, dtype=np.int32)
+        cS = np.ascontiguousarray(corr_S, dtype=np.float64).reshape(-1, 8)
+        ev = np.ascontiguousarray(edge_v, dtype=np.int32).reshape(-1, 2)
+        kind = np.ascontiguousarray(edge_kind, dtype=np.int32)
+        pos = _f32(pt_pos).reshape(-1, 3)
+        ref = np.ascontiguousarray(pt_ref, dtype=np.int32)
+        K, E, P = len(T), len(ev), len(pos)
+        if len(corr) != K or len(kind) != E or len(ref) != P:
+            raise ValueError("table sizes differ")
+        if max_env_blocks is None:
+            max_env_blocks = K * (K + 1) // 2 if dense else essential_graph_envelope(K, loop_kf, ev)
+        off = [np.array([0, n], np.int32) for n in (K, E, P)]
+        loop = np.array([loop_kf], np.int32)
+        out = dict(Tcw=np.zeros((K, 12), np.float32), pos=np.zeros((P, 3), np.float32), Scw=np.zeros((K, 8)),
+                   trace=np.zeros(2, np.int32), chi2=np.zeros(2))
+        status = np.zeros(1, np.int32)
+        ptr = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+        q = L.EssentialGraphBatch()
+        q.batch = 1
+        q.kf_off, q.n_kf, q.kf_Tcw, q.kf_corr = ptr(off[0]), K, ptr(T), ptr(corr)
+        q.corr_S, q.n_corr, q.loop_kf = ptr(cS), len(cS), ptr(loop)
+        q.edge_off, q.n_edges, q.edge_v, q.edge_kind = ptr(off[1]), E, ptr(ev), ptr(kind)
+        q.pt_off, q.n_pt, q.pt_pos, q.pt_ref = ptr(off[2]), P, ptr(pos), ptr(ref)
+        q.fix_scale, q.iterations, q.max_env_blocks, q.dense = int(bool(fix_scale)), int(iterations), int(max_env_blocks), int(dense)
+        q.kf_Tcw_opt, q.pt_pos_opt, q.Scw_opt = ptr(out["Tcw"]), ptr(out["pos"]), ptr(out["Scw"])
+        q.trace, q.chi2, q.status = ptr(out["trace"]), ptr(out["chi2"]), ptr(status)
+        L.check(L.lib().orbx_optimize_essential_graph(self._h, C.byref(q)))
+        out["status"] = int(status[0])
+        return out
+
+    def essential_graph_batch_device(self, d_kf_off, d_kf_Tcw, d_kf_corr, d_corr_S, d_loop_kf, d_edge_off, d_edge_v,
+                                     d_edge_kind, d_pt_off, d_pt_pos, d_pt_ref, fix_scale: bool, max_env_blocks: int,
+                                     d_kf_Tcw_opt, d_pt_pos_opt, d_status, d_Scw_opt=None, d_trace=None, d_chi2=None,
+                                     iterations: int = 0, dense: bool = False, stream=None) -> None:
+        """orbx_optimize_essential_graph_batch_device on device tensors: d_kf_off / d_edge_off /
+        d_pt_off (B + 1,) i32, d_kf_Tcw / d_kf_Tcw_opt (n_kf, 12) f32, d_kf_corr (n_kf,) i32,
+        d_corr_S (n_corr, 8) f64, d_loop_kf (B,) i32, d_edge_v (n_edges, 2) / d_edge_kind
+        (n_edges,) i32, d_pt_pos / d_pt_pos_opt (n_pt, 3) f32, d_pt_ref (n_pt,) i32, d_status
+        (B,) i32, d_Scw_opt (n_kf, 8) f64, d_trace (B, 2) i32, d_chi2 (B, 2) f64.  Asynchronous
+        on `stream` (or the handle's)."""
+        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())  # noqa: E731
+        q = L.EssentialGraphBatch()
+        q.batch = int(d_kf_off.shape[0]) - 1
+        q.kf_off, q.n_kf, q.kf_Tcw, q.kf_corr = ptr(d_kf_off), int(d_kf_Tcw.shape[0]), ptr(d_kf_Tcw), ptr(d_kf_corr)
+        q.corr_S, q.n_corr, q.loop_kf = ptr(d_corr_S), int(d_corr_S.shape[0]), ptr(d_loop_kf)
+        q.edge_off, q.n_edges, q.edge_v, q.edge_kind = ptr(d_edge_off), int(d_edge_v.shape[0]), ptr(d_edge_v), ptr(d_edge_kind)
+        q.pt_off, q.n_pt, q.pt_pos, q.pt_ref = ptr(d_pt_off), int(d_pt_pos.shape[0]), ptr(d_pt_pos), ptr(d_pt_ref)
+        q.fix_scale, q.iterations, q.max_env_blocks, q.dense = int(bool(fix_scale)), int(iterations), int(max_env_blocks), int(dense)
+        q.kf_Tcw_opt, q.pt_pos_opt, q.Scw_opt = ptr(d_kf_Tcw_opt), ptr(d_pt_pos_opt), ptr(d_Scw_opt)
+        q.trace, q.chi2, q.status = ptr(d_trace), ptr(d_chi2), ptr(d_status)
+        s = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        L.check(L.lib().orbx_optimize_essential_graph_batch_device(self._h, C.byref(q), s))
