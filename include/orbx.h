@@ -1286,6 +1286,96 @@ int orbx_local_bundle_adjustment_batch_device(orbx_matcher* m, const orbx_local_
  * synchronisation; the same bytes as the batch form gives that problem. */
 int orbx_local_bundle_adjustment(orbx_matcher* m, const orbx_local_ba_batch* lba);
 
+/* ---- Optimizer::BundleAdjustment / GlobalBundleAdjustemnt: batched envelope Schur-complement LM ----
+ * Optimizer::BundleAdjustment (src/Optimizer.cc:41-281) from the assembled graph (cc:79-233) to
+ * the recovered estimates (cc:236-280), as Tracking::CreateInitialMapMonocular (Tracking.cc:761,
+ * 20 iterations) and LoopClosing::RunGlobalBundleAdjustment (LoopClosing.cc:715, 10 iterations)
+ * call it, for B maps in HBM in one launch: one persistent workgroup per problem runs
+ * initializeOptimization() and one optimize(iterations) with the g2o of the local bundle
+ * adjustment above (the same edges, Jacobians, quadratic form, Huber kernel, Schur complement
+ * and Levenberg-Marquardt).  There are no chi2 or depth tests, no second optimisation and no
+ * erase flags, and no cap on the keyframes: the reduced system S is a block envelope (skyline)
+ * of 6 x 6 blocks in table order, factored by the LDL^T of the essential graph below, which
+ * gives the bytes of the dense factorisation; only an exactly zero (or non-finite) pivot is a
+ * failed solve, which is a rejected trial.  The stop flag (pbStopFlag) is not supported: the
+ * iteration count is the caller's lever.  Float inputs are widened to double, everything after
+ * is double (but the two float intermediates of the stereo projection), outputs are rounded to
+ * float once.  Every sum has one owner and a fixed shape (no floating-point atomics) and no
+ * workgroup waits on another: a problem's results are the same bytes whatever the batch around
+ * it.  DESIGN.md §4.23.  With the caller: which keyframes and points are good (bad ones are
+ * not passed), whether the results go to SetPose / SetWorldPos or to mTcwGBA / mPosGBA (the
+ * nLoopKF switch), the spanning-tree propagation of LoopClosing.cc:740-800,
+ * ComputeSceneMedianDepth and the rescale of the initial map.
+ *   The tables are those of orbx_local_ba_batch, with the same rules for observations that
+ *   are no edges (ORBX_GLOBAL_BA_STATUS_BAD_INDEX).  Edge order is point order, then the
+ *   caller's order within a point (the reference's orders are pointer orders); the order of S
+ *   is table order.  kf_fixed: mnId == 0 in the reference.  An edge is monocular iff
+ *   u_right < 0; the Huber deltas are the floats sqrt(5.99) (cc:115 -- not the local bundle
+ *   adjustment's 5.991) and sqrt(7.815), used iff robust != 0 (bRobust).
+ *   iterations: nIterations; 0 means 10.  max_env_blocks: orbx_global_ba_envelope gives a
+ *   problem's.  dense != 0 forces the full envelope (first[f] = 0; a test switch: the same
+ *   bytes, F (F + 1) / 2 blocks).
+ *   Outputs: kf_Tcw_opt = Converter::toCvMat(SE3Quat) of EVERY keyframe (cc:236-254 writes the
+ *   fixed ones too, so a fixed pose comes back as its round trip through the normalised
+ *   quaternion, not as its input bytes); pt_pos_opt; pt_included[j] = 0 for a point without an
+ *   edge (vbNotIncludedMP, cc:223-228), which keeps its input bytes; trace = {LM iterations,
+ *   linear solves}; chi2 = {initial, final} active robust chi2; status = the
+ *   ORBX_GLOBAL_BA_STATUS_* bits.  A keyframe that may move but has no edge is not active and
+ *   keeps its estimate.  A problem without a keyframe that may move (NO_FREE_KF; the reference
+ *   is undefined for it), or whose envelope has more than max_env_blocks blocks (CAPACITY),
+ *   returns its inputs' bytes, pt_included = 0 and a zero trace and chi2.  With no edge, or none
+ *   at a keyframe that may move, no iteration runs.
+ * inv_level_sigma2 is a host array; every other pointer is a device pointer.  trace and chi2
+ * may be NULL.  Asynchronous on `stream` (or the matcher's). */
+#define ORBX_GLOBAL_BA_STATUS_CAPACITY 1
+#define ORBX_GLOBAL_BA_STATUS_NO_FREE_KF 2
+#define ORBX_GLOBAL_BA_STATUS_BAD_INDEX 4
+typedef struct {
+    int batch;
+    const int32_t* kf_off;           /* [B + 1] */
+    int n_kf;                        /* rows of the keyframe table */
+    const float* kf_Tcw;             /* [n_kf][12] GetPose(), rows 0..2 */
+    const uint8_t* kf_fixed;         /* [n_kf] */
+    const int32_t* kf_slot;          /* [n_kf] row of kps / u_right */
+    const int32_t* pt_off;           /* [B + 1] */
+    int n_pt;                        /* rows of the point table */
+    const float* pt_pos;             /* [n_pt][3] GetWorldPos() */
+    const int32_t* obs_off;          /* [n_pt + 1] */
+    int n_obs;
+    const int32_t* obs_kf;           /* [n_obs] */
+    const int32_t* obs_kp;           /* [n_obs] */
+    int n_slots, cap;
+    const orbx_keypoint* kps;        /* [n_slots][cap] mvKeysUn */
+    const float* u_right;            /* [n_slots][cap] mvuRight, or NULL */
+    const float* inv_level_sigma2;   /* host: mvInvLevelSigma2 (nlevels) */
+    int nlevels;
+    float fx, fy, cx, cy, bf;
+    int iterations;                  /* nIterations; 0: 10 */
+    int robust;                      /* bRobust */
+    int64_t max_env_blocks;          /* 6 x 6 blocks per problem that the workspace is sized for */
+    int dense;                       /* test switch: the full envelope */
+    float* kf_Tcw_opt;               /* [n_kf][12] out */
+    float* pt_pos_opt;               /* [n_pt][3] out */
+    uint8_t* pt_included;            /* [n_pt] out */
+    int32_t* trace;                  /* [B][2] out or NULL */
+    double* chi2;                    /* [B][2] out or NULL */
+    int32_t* status;                 /* [B] out */
+} orbx_global_ba_batch;
+int orbx_global_bundle_adjustment_batch_device(orbx_matcher* m, const orbx_global_ba_batch* ga, void* stream);
+
+/* The single-problem host form: every pointer of the struct is a host pointer and batch is 1
+ * (kf_off = {0, n_kf}, pt_off = {0, n_pt}).  One upload, the batch kernel with B = 1, one
+ * synchronisation; the same bytes as the batch form gives that problem. */
+int orbx_global_bundle_adjustment(orbx_matcher* m, const orbx_global_ba_batch* ga);
+
+/* The blocks of one problem's envelope: over the keyframes that are not fixed and have an
+ * observation (an edge here: obs_kf in [0, n_kf) -- keypoints, slots, octaves and u_right are
+ * not looked at, so this is an upper bound where the kernel finds observations that are no
+ * edges), indexed in table order, sum of f - first[f] + 1 with first[f] the smallest index
+ * among f and the keyframes that share a point with it.  Host only, no GPU. */
+int orbx_global_ba_envelope(int n_kf, const uint8_t* kf_fixed, int n_pt, const int32_t* obs_off,
+                            const int32_t* obs_kf, int n_obs, int64_t* blocks);
+
 /* ---- Optimizer::OptimizeEssentialGraph: batched Sim3 pose-graph Levenberg-Marquardt ----
  * Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:873-1150) from the assembled graph to
  * the recovered estimates, as LoopClosing::CorrectLoop calls it (LoopClosing.cc:621), with the
@@ -1301,7 +1391,8 @@ int orbx_local_bundle_adjustment(orbx_matcher* m, const orbx_local_ba_batch* lba
  * a failed solve, which is a rejected trial.  There is no cap on keyframes.  DESIGN.md §4.22.
  * Out of scope, with the caller: CorrectLoop's Sim3 propagation and first map-point
  * correction (LoopClosing.cc:488-571), UpdateConnections, SearchAndFuse,
- * UpdateNormalAndDepth, building the graph on the device, and global BA.
+ * UpdateNormalAndDepth and building the graph on the device (the global bundle adjustment
+ * that follows is orbx_global_bundle_adjustment_batch_device above).
  *   Problem b owns rows kf_off[b] .. kf_off[b + 1] of the keyframe table (the good keyframes
  *   in ascending mnId), edge_off[b] .. of the edge table and pt_off[b] .. of the point table
  *   (offsets over the whole tables, ascending).  kf_Tcw is the pose that gives the

@@ -398,6 +398,77 @@ public:
         return n_erase;
     }
 
+    // BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust)
+    // (src/Optimizer.cc:41-281), which GlobalBundleAdjustemnt calls with the whole map, from the
+    // assembled graph on: the tables of LocalBundleAdjustment above with the good keyframes and
+    // points of the map, kfFixed = (mnId == 0).  The stop flag is not supported, and where the
+    // results go (SetPose / SetWorldPos or mTcwGBA / mPosGBA, the nLoopKF switch) is the
+    // caller's business: kfTcw (every keyframe, the fixed ones as their round trip through the
+    // quaternion) and mpPos are updated in place; vbNotIncludedMP gets one flag per point (1: the
+    // point has no edge and keeps its position).  trace (optional, 2 ints): the LM iterations
+    // run and the linear solves tried; chi2 (optional, 2 doubles): initial and final.  Returns
+    // the ORBX_GLOBAL_BA_STATUS_* bits.
+    static int BundleAdjustment(ORBmatcher& matcher, std::vector<float>& kfTcw, const std::vector<uint8_t>& kfFixed,
+                                const std::vector<int32_t>& kfSlot, std::vector<float>& mpPos,
+                                const std::vector<int32_t>& obsOff, const std::vector<int32_t>& obsKF,
+                                const std::vector<int32_t>& obsKP, const std::vector<orbx_keypoint>& mvKeysUn,
+                                const std::vector<float>& mvuRight, int cap, const std::vector<float>& mvInvLevelSigma2,
+                                float fx, float fy, float cx, float cy, float mbf, int nIterations = 5,
+                                bool bRobust = true, std::vector<uint8_t>* vbNotIncludedMP = nullptr,
+                                int32_t* trace = nullptr, double* chi2 = nullptr) {
+        const int32_t nkf = (int32_t)kfFixed.size(), npt = (int32_t)(mpPos.size() / 3), nobs = (int32_t)obsKF.size();
+        if (cap <= 0 || kfTcw.size() != (size_t)nkf * 12 || kfSlot.size() != (size_t)nkf ||
+            obsOff.size() != (size_t)npt + 1 || obsKP.size() != (size_t)nobs || mvKeysUn.size() % (size_t)cap ||
+            (!mvuRight.empty() && mvuRight.size() != mvKeysUn.size()))
+            throw std::runtime_error("BundleAdjustment: array sizes differ");
+        const int32_t kf_off[2] = {0, nkf}, pt_off[2] = {0, npt};
+        std::vector<float> Tout(kfTcw.size()), Xout(mpPos.size());
+        std::vector<uint8_t> included((size_t)npt + 1, 0);
+        int32_t st = 0;
+        orbx_global_ba_batch q{};
+        check(orbx_global_ba_envelope(nkf, kfFixed.data(), npt, obsOff.data(), obsKF.data(), nobs, &q.max_env_blocks));
+        q.batch = 1;
+        q.kf_off = kf_off;
+        q.n_kf = nkf;
+        q.kf_Tcw = kfTcw.data();
+        q.kf_fixed = kfFixed.data();
+        q.kf_slot = kfSlot.data();
+        q.pt_off = pt_off;
+        q.n_pt = npt;
+        q.pt_pos = mpPos.data();
+        q.obs_off = obsOff.data();
+        q.n_obs = nobs;
+        q.obs_kf = obsKF.data();
+        q.obs_kp = obsKP.data();
+        q.n_slots = (int)(mvKeysUn.size() / (size_t)cap);
+        q.cap = cap;
+        q.kps = mvKeysUn.data();
+        q.u_right = mvuRight.empty() ? nullptr : mvuRight.data();
+        q.inv_level_sigma2 = mvInvLevelSigma2.data();
+        q.nlevels = (int)mvInvLevelSigma2.size();
+        q.fx = fx;
+        q.fy = fy;
+        q.cx = cx;
+        q.cy = cy;
+        q.bf = mbf;
+        q.iterations = nIterations;
+        q.robust = bRobust ? 1 : 0;
+        q.kf_Tcw_opt = Tout.data();
+        q.pt_pos_opt = Xout.data();
+        q.pt_included = included.data();
+        q.trace = trace;
+        q.chi2 = chi2;
+        q.status = &st;
+        check(orbx_global_bundle_adjustment(matcher.handle(), &q));
+        kfTcw = Tout;
+        mpPos = Xout;
+        if (vbNotIncludedMP) {
+            vbNotIncludedMP->resize((size_t)npt);
+            for (int32_t j = 0; j < npt; j++) (*vbNotIncludedMP)[(size_t)j] = included[(size_t)j] ? 0 : 1;
+        }
+        return st;
+    }
+
     // OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3,
     // LoopConnections, bFixScale) (src/Optimizer.cc:873-1150) from the assembled graph on: the
     // good keyframes' non-corrected poses kfTcw (12 floats each, rows 0..2, ascending mnId),

@@ -61,6 +61,7 @@ EXPORTED = [
     "orbx_pnp_iterate_device", "orbx_pnp_set", "orbx_pnp_iterate", "orbx_pnp_draws", "orbx_optimize_sim3_batch_device", "orbx_optimize_sim3",
     "orbx_triangulate_pairs_batch_device", "orbx_triangulate_pairs",
     "orbx_local_bundle_adjustment_batch_device", "orbx_local_bundle_adjustment",
+    "orbx_global_bundle_adjustment_batch_device", "orbx_global_bundle_adjustment", "orbx_global_ba_envelope",
     "orbx_optimize_essential_graph_batch_device", "orbx_optimize_essential_graph", "orbx_essential_graph_envelope",
     "orbx_initializer_create", "orbx_initializer_destroy", "orbx_initializer_initialize_device",
     "orbx_initializer_initialize", "orbx_initializer_sets",
@@ -207,6 +208,24 @@ ORBX_LOCAL_BA_MAX_FREE_KF = 64
 ORBX_LOCAL_BA_STATUS_CAPACITY = 1
 ORBX_LOCAL_BA_STATUS_NO_FREE_KF = 2
 ORBX_LOCAL_BA_STATUS_BAD_INDEX = 4
+
+
+class GlobalBaBatch(C.Structure):
+    """orbx_global_ba_batch."""
+    _fields_ = [("batch", C.c_int), ("kf_off", C.c_void_p), ("n_kf", C.c_int), ("kf_Tcw", C.c_void_p),
+                ("kf_fixed", C.c_void_p), ("kf_slot", C.c_void_p), ("pt_off", C.c_void_p), ("n_pt", C.c_int),
+                ("pt_pos", C.c_void_p), ("obs_off", C.c_void_p), ("n_obs", C.c_int), ("obs_kf", C.c_void_p),
+                ("obs_kp", C.c_void_p), ("n_slots", C.c_int), ("cap", C.c_int), ("kps", C.c_void_p),
+                ("u_right", C.c_void_p), ("inv_level_sigma2", C.POINTER(C.c_float)), ("nlevels", C.c_int),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float),
+                ("iterations", C.c_int), ("robust", C.c_int), ("max_env_blocks", C.c_int64), ("dense", C.c_int),
+                ("kf_Tcw_opt", C.c_void_p), ("pt_pos_opt", C.c_void_p), ("pt_included", C.c_void_p),
+                ("trace", C.c_void_p), ("chi2", C.c_void_p), ("status", C.c_void_p)]
+
+
+ORBX_GLOBAL_BA_STATUS_CAPACITY = 1
+ORBX_GLOBAL_BA_STATUS_NO_FREE_KF = 2
+ORBX_GLOBAL_BA_STATUS_BAD_INDEX = 4
 
 
 class EssentialGraphBatch(C.Structure):
@@ -475,6 +494,9 @@ def lib() -> C.CDLL:
     L.orbx_optimize_sim3.argtypes = [vp, C.POINTER(OptimizeSim3Batch)]
     L.orbx_local_bundle_adjustment_batch_device.argtypes = [vp, C.POINTER(LocalBaBatch), vp]
     L.orbx_local_bundle_adjustment.argtypes = [vp, C.POINTER(LocalBaBatch)]
+    L.orbx_global_bundle_adjustment_batch_device.argtypes = [vp, C.POINTER(GlobalBaBatch), vp]
+    L.orbx_global_bundle_adjustment.argtypes = [vp, C.POINTER(GlobalBaBatch)]
+    L.orbx_global_ba_envelope.argtypes = [C.c_int, vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int64)]
     L.orbx_optimize_essential_graph_batch_device.argtypes = [vp, C.POINTER(EssentialGraphBatch), vp]
     L.orbx_optimize_essential_graph.argtypes = [vp, C.POINTER(EssentialGraphBatch)]
     L.orbx_essential_graph_envelope.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_int64)]

@@ -29,7 +29,9 @@
 // holds the 7 x 7 blocks (g, f), g = first[f] .. f, where first[f] is the smallest index among
 // f and its neighbours.  H, its factor, b, the solution and every work vector live in the
 // HBM workspace: 7 F doubles pass the LDS of a compute unit near F = 2900, and one path for
-// every size is worth more than the LDS's latency at small ones.
+// every size is worth more than the LDS's latency at small ones.  The scan,
+// the owner's sort, the row lists and the solver are orbx_envelope.h's, shared with
+// orbx_globalba.hip and instantiated here with 7 x 7 blocks.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -39,6 +41,7 @@
 #include <type_traits>
 
 #include "orbx.h"
+#include "orbx_envelope.h"
 #include "orbx_error.h"
 #include "orbx_kernels.h"
 #include "orbx_layout.h"
@@ -52,64 +55,14 @@ namespace {
 constexpr int kEgThreads = 256;
 constexpr int kEgWaves = kEgThreads / 64;
 
-// Exclusive prefix sums of value(0 .. n-1) into out[0 .. n] (out[n] = the total, also returned
-// to every thread), in chunks of the workgroup, in index order.
-template <class T, class F>
-__device__ __forceinline__ T block_scan(F value, T* out, int n, T* s_scan) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    T carry = 0;
-    for (int c0 = 0; c0 < n; c0 += kEgThreads) {
-        const int i = c0 + tid;
-        const T v = i < n ? value(i) : (T)0;
-        T inc = v;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const T o = __shfl_up(inc, m, 64);
-            if (lane >= m) inc += o;
-        }
-        if (lane == 63) s_scan[wave] = inc;
-        __syncthreads();
-        T off = carry, total = 0;
-#pragma unroll
-        for (int w = 0; w < kEgWaves; w++) {
-            if (w < wave) off += s_scan[w];
-            total += s_scan[w];
-        }
-        if (i < n) out[i] = off + inc - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (tid == 0) out[n] = carry;
-    return carry;
-}
+static_assert(kEgThreads == env::kThreads, "orbx_envelope.h is written for this workgroup");
+using env::block_scan;
+using env::sort_ascending;
 
-// l[0 .. n) into ascending order in place, by one thread: a heapsort, so that a hub keyframe
-// with thousands of edges costs n log n.
-__device__ __forceinline__ void sort_ascending(int32_t* l, int n) {
-    auto sift = [&](int root, int end) {
-        const int key = l[root];
-        for (;;) {
-            int c = 2 * root + 1;
-            if (c >= end) break;
-            if (c + 1 < end && l[c + 1] > l[c]) c++;
-            if (l[c] <= key) break;
-            l[root] = l[c];
-            root = c;
-        }
-        l[root] = key;
-    };
-    for (int i = n / 2 - 1; i >= 0; i--) sift(i, n);
-    for (int end = n - 1; end > 0; end--) {
-        const int top = l[0];
-        l[0] = l[end];
-        l[end] = top;
-        sift(0, end);
-    }
-}
-
-// One problem's rows and its regions of the workspace.
-struct Prob {
-    int K, E, P, loop, F;
+// One problem's rows and its regions of the workspace; the envelope H, its factor L, b, x,
+// the work vectors and the envelope's index lists are env::Envelope's.
+struct Prob : env::Envelope {
+    int K, E, P, loop;
     bool fix_scale;
     const int32_t* ev;    // [E][2]
     const S3* probes;     // [14] kernel arguments
@@ -117,10 +70,7 @@ struct Prob {
     double* meas;         // [E][8]
     double* J;            // [E][2][49]: the Jacobian of vertex 0 / 1, column d at [7 d .. 7 d + 6]
     double* err;          // [E][7]
-    double *H, *L;        // the envelope and its factor
-    double *b, *x, *xs, *ys;
-    int32_t *ok, *free_idx, *free_kf, *first, *adj_off, *adj, *deg, *rows;
-    long long *col_off, *row_off;
+    int32_t *ok, *free_idx, *free_kf, *adj_off, *adj, *deg;
     double* s_red;
 };
 
@@ -227,152 +177,6 @@ __device__ __forceinline__ void build_system(const Prob& Q) {
             Q.b[7 * f + a] = acc;
     }
     __syncthreads();
-}
-
-__device__ __forceinline__ double* diag_block(const Prob& Q, double* M, int f) {
-    return M + (size_t)(Q.col_off[f] + f - Q.first[f]) * 49;
-}
-
-// (H + lambda I) x = b by the block-envelope LDL^T without pivoting.  Every entry of the
-// factor and of the substitutions receives the terms lm::ldlt_solve_block gives it, in its
-// order; the terms outside the envelope are exact zeros.  Only a pivot that is exactly zero
-// (or not finite) is a failed solve; Q.x is then left as it was.
-__device__ __forceinline__ bool solve(const Prob& Q, double lam) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int F = Q.F, n = 7 * F;
-    const size_t words = (size_t)Q.col_off[F] * 49;
-    for (size_t i = tid; i < words; i += kEgThreads) Q.L[i] = Q.H[i];
-    __syncthreads();
-    for (int i = tid; i < n; i += kEgThreads) {
-        const int f = i / 7, r = i - 7 * f;
-        double* dd = diag_block(Q, Q.L, f) + 8 * r;
-        *dd = *dd + lam;
-        Q.xs[i] = Q.b[i];
-    }
-    __syncthreads();
-    // The factorisation and the forward substitution, one block pivot at a time
-    for (int g = 0; g < F; g++) {
-        // the pivot block, by every thread: the 7 scalar pivots in order
-        double U[7][7], d[7], y[7];
-        {
-            const double* blk = diag_block(Q, Q.L, g);
-#pragma unroll
-            for (int r = 0; r < 7; r++)
-#pragma unroll
-                for (int k = r; k < 7; k++) U[r][k] = blk[7 * r + k];
-        }
-        bool ok = true;
-#pragma unroll
-        for (int r = 0; r < 7; r++) {
-            d[r] = U[r][r];
-            if (d[r] == 0.0 || !isfinite(d[r])) ok = false;
-#pragma unroll
-            for (int k = r + 1; k < 7; k++) U[r][k] = U[r][k] / d[r];
-#pragma unroll
-            for (int i = r + 1; i < 7; i++)
-#pragma unroll
-                for (int k = i; k < 7; k++) U[i][k] = U[i][k] - U[r][i] * U[r][k] * d[r];
-        }
-        if (!ok) return false;  // the same for every thread
-#pragma unroll
-        for (int r = 0; r < 7; r++) {
-            double t = Q.xs[7 * g + r];
-#pragma unroll
-            for (int k = 0; k < r; k++) t = t - U[k][r] * y[k];
-            y[r] = t;
-        }
-        // block row g: one thread per scalar column of the columns that reach up to g
-        const long long r0 = Q.row_off[g];
-        const int m = (int)(Q.row_off[g + 1] - r0);
-        for (int w = tid; w < 7 * m; w += kEgThreads) {
-            const int q = Q.rows[r0 + w / 7], cc = w % 7;
-            double* blk = Q.L + (size_t)(Q.col_off[q] + g - Q.first[q]) * 49 + cc;
-            double u[7];
-#pragma unroll
-            for (int r = 0; r < 7; r++) u[r] = blk[7 * r];
-#pragma unroll
-            for (int r = 0; r < 7; r++) {
-                u[r] = u[r] / d[r];
-#pragma unroll
-                for (int i = r + 1; i < 7; i++) u[i] = u[i] - U[r][i] * u[r] * d[r];
-            }
-            double t = Q.xs[7 * q + cc];
-#pragma unroll
-            for (int r = 0; r < 7; r++) {
-                blk[7 * r] = u[r];
-                t = t - u[r] * y[r];
-            }
-            Q.xs[7 * q + cc] = t;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double* blk = diag_block(Q, Q.L, g);
-#pragma unroll
-            for (int r = 0; r < 7; r++) {
-                blk[8 * r] = d[r];
-#pragma unroll
-                for (int k = r + 1; k < 7; k++) blk[7 * r + k] = U[r][k];
-                Q.ys[7 * g + r] = y[r];
-            }
-        }
-        // the trailing blocks (qa, qb), qa <= qb, of the row's columns: one wave each
-        const long long pairs = (long long)m * (m + 1) / 2;
-        for (long long p = wave; p < pairs; p += kEgWaves) {
-            long long ib = (long long)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
-            while (ib * (ib + 1) / 2 > p) ib--;
-            while ((ib + 1) * (ib + 2) / 2 <= p) ib++;
-            const long long ia = p - ib * (ib + 1) / 2;
-            if (lane >= 49) continue;
-            const int ra = lane / 7, cb = lane % 7;
-            if (ia == ib && ra > cb) continue;
-            int qa = Q.rows[r0 + ia], qb = Q.rows[r0 + ib];
-            if (qa > qb) {  // a row's columns are in no particular order
-                const int q = qa;
-                qa = qb;
-                qb = q;
-            }
-            const double* ua = Q.L + (size_t)(Q.col_off[qa] + g - Q.first[qa]) * 49 + ra;
-            const double* ub = Q.L + (size_t)(Q.col_off[qb] + g - Q.first[qb]) * 49 + cb;
-            double* tgt = Q.L + (size_t)(Q.col_off[qb] + qa - Q.first[qb]) * 49 + lane;
-            double t = *tgt;
-#pragma unroll
-            for (int r = 0; r < 7; r++) t = t - ua[7 * r] * ub[7 * r] * d[r];
-            *tgt = t;
-        }
-        __syncthreads();
-    }
-    for (int i = tid; i < n; i += kEgThreads) {
-        const int f = i / 7, r = i - 7 * f;
-        Q.xs[i] = Q.ys[i] / diag_block(Q, Q.L, f)[8 * r];
-    }
-    __syncthreads();
-    // The back substitution, one block column at a time, the columns descending
-    for (int f = F - 1; f >= 0; f--) {
-        const double* blk = diag_block(Q, Q.L, f);
-        double xf[7];
-#pragma unroll
-        for (int cc = 6; cc >= 0; cc--) {
-            double t = Q.xs[7 * f + cc];
-#pragma unroll
-            for (int k = 6; k > cc; k--) t = t - blk[7 * cc + k] * xf[k];
-            xf[cc] = t;
-        }
-        if (tid == 0) {
-#pragma unroll
-            for (int cc = 0; cc < 7; cc++) Q.x[7 * f + cc] = xf[cc];
-        }
-        const int f0 = Q.first[f];
-        const double* col = Q.L + (size_t)Q.col_off[f] * 49;
-        for (int w = tid; w < 7 * (f - f0); w += kEgThreads) {
-            const double* u = col + (size_t)(w / 7) * 49 + 7 * (w % 7);
-            double t = Q.xs[7 * f0 + w];
-#pragma unroll
-            for (int cc = 6; cc >= 0; cc--) t = t - u[cc] * xf[cc];
-            Q.xs[7 * f0 + w] = t;
-        }
-        __syncthreads();
-    }
-    return true;
 }
 
 __device__ __forceinline__ void return_inputs(const EssGraphArgs& A, const Prob& Q, int k0, int p0, int b, int status) {
@@ -526,27 +330,7 @@ __global__ __launch_bounds__(kEgThreads) void k_essential_graph(EssGraphArgs A) 
         return_inputs(A, Q, k0, p0, b, ORBX_ESSENTIAL_GRAPH_STATUS_CAPACITY | (nbad > 0 ? ORBX_ESSENTIAL_GRAPH_STATUS_BAD_INDEX : 0));
         return;
     }
-    // Block row g holds the columns q with first[q] <= g < q: their number is a running sum of
-    // +1 at first[q] and -1 at q, and one wave per column enters it into its rows.  The order
-    // of a row's columns only decides which thread works on which block, never the order of
-    // an entry's terms, so the lists need no sorting.  All of it is linear in the envelope.
-    for (int g = tid; g < F; g += kEgThreads) Q.deg[g] = 0;
-    __syncthreads();
-    for (int q = tid; q < F; q += kEgThreads)
-        if (Q.first[q] < q) {
-            atomicAdd(&Q.deg[Q.first[q]], 1);
-            atomicAdd(&Q.deg[q], -1);
-        }
-    __syncthreads();
-    block_scan<long long>([&](int g) { return (long long)degree(g); }, Q.row_off, F, s_scan);
-    __syncthreads();
-    block_scan<long long>([&](int g) { return Q.row_off[g] + degree(g); }, Q.row_off, F, s_scan);
-    __syncthreads();
-    for (int g = tid; g < F; g += kEgThreads) Q.deg[g] = 0;
-    __syncthreads();
-    for (int q = tid >> 6; q < F; q += kEgWaves)
-        for (int g = Q.first[q] + (tid & 63); g < q; g += 64) Q.rows[Q.row_off[g] + atomicAdd(&Q.deg[g], 1)] = q;
-    __syncthreads();
+    env::row_lists(Q, Q.deg, s_scan);
 
     // SparseOptimizer::optimize with OptimizationAlgorithmLevenberg, as orbx_optsim3.hip's
     const int max_its = A.iterations > 0 ? A.iterations : 20;
@@ -575,7 +359,7 @@ __global__ __launch_bounds__(kEgThreads) void k_essential_graph(EssGraphArgs A) 
             double rho = 0.0;
             do {
                 const long long c1 = wall_clock64();
-                const bool ok = solve(Q, lam);
+                const bool ok = env::solve<7, true>(Q, lam);
                 __syncthreads();
                 t_solve += wall_clock64() - c1;
                 // push, oplus (exp(x) * estimate; _fix_scale zeroes the solver's entry in place), computeScale

@@ -233,6 +233,64 @@ struct LocalBaArgs {
 size_t local_ba_workspace_bytes(int batch, int n_kf, int n_pt, int n_obs, int max_free);
 hipError_t launch_local_ba(LocalBaArgs A, int batch, char* workspace, hipStream_t stream);
 
+// k_global_ba (orbx_globalba.hip): Optimizer::BundleAdjustment for `batch` maps, one workgroup
+// each; everything sized by a problem's keyframes, points or observations, and the block
+// envelope of the reduced system S, lives in the workspace.
+struct GlobalBaArgs {
+    const int32_t* kf_off;       // [B + 1]
+    int n_kf;
+    const float* kf_Tcw;         // [n_kf][12]
+    const uint8_t* kf_fixed;     // [n_kf]
+    const int32_t* kf_slot;      // [n_kf]
+    const int32_t* pt_off;       // [B + 1]
+    int n_pt;
+    const float* pt_pos;         // [n_pt][3]
+    const int32_t* obs_off;      // [n_pt + 1]
+    int n_obs;
+    const int32_t* obs_kf;       // [n_obs]
+    const int32_t* obs_kp;       // [n_obs]
+    int n_slots, cap;
+    const orbx_keypoint* kps;    // [n_slots][cap]
+    const float* u_right;        // [n_slots][cap] or null
+    float inv_sigma2[ORBX_MAX_LEVELS];
+    int nlevels;
+    float fx, fy, cx, cy, bf;
+    float delta_mono, delta_stereo;
+    int iterations, robust, dense;
+    long long max_env_blocks;    // 6 x 6 blocks per problem that S is sized for
+    float* kf_Tcw_out;           // [n_kf][12]
+    float* pt_pos_out;           // [n_pt][3]
+    uint8_t* pt_included;        // [n_pt]
+    int32_t* trace;              // [B][2] or null
+    double* chi2;                // [B][2] or null
+    int32_t* status;             // [B]
+    // set by launch_global_ba
+    double* pose;                // [n_kf][2][16]: current and trial {q xyzw, t, R row by row}
+    double* pt;                  // [n_pt][2][3]: current and trial
+    double* pt_sys;              // [n_pt][24]: Hll (6), bl (3), Dinv (9), Dinv bl (3), xl (3)
+    double* W;                   // [n_obs][18]: A^T (rho' Omega) B
+    double* L;                   // [B][max_env_blocks][36]: S, factored in place
+    double* hpp;                 // [n_kf][21]: the upper triangle of a block column's Hpp
+    double* vec;                 // [n_kf][5][6]: b_p, b_s, x and the two work vectors of the solve
+    long long* col_off;          // [n_kf + B] first block of a column (F + 1 per problem)
+    long long* row_off;          // [n_kf + B] first entry of a block row in rows
+    float* rec;                  // [n_obs][4]: u, v, u_right, invSigma2
+    int32_t* rows;               // [B][max_env_blocks] the columns of every block row
+    int32_t* rec_kf;             // [n_obs] keyframe row, -1: not an edge
+    int32_t* rec_pt;             // [n_obs] point row
+    int32_t* rec_flags;          // [n_obs]
+    int32_t* rec_free;           // [n_obs] block column in S, -1: none
+    int32_t* kf_elist;           // [n_obs] the edges of each block column, in edge order
+    int32_t* kf_free;            // [n_kf] block column in S, -1: none
+    int32_t* free_kf;            // [n_kf] its inverse
+    int32_t* deg;                // [n_kf] counters
+    int32_t* first;              // [n_kf + B]
+    int32_t* eoff;               // [n_kf + B] first edge of a block column in kf_elist
+    int32_t* pt_active;          // [n_pt]
+};
+size_t global_ba_workspace_bytes(int batch, int n_kf, int n_pt, int n_obs, long long max_env_blocks);
+hipError_t launch_global_ba(GlobalBaArgs A, int batch, char* workspace, hipStream_t stream);
+
 // k_essential_graph (orbx_essgraph.hip): Optimizer::OptimizeEssentialGraph for `batch` maps,
 // one workgroup each; the estimates, the measurements, the Jacobians, the block envelope of H,
 // its factor and every vector live in the workspace.

@@ -1,5 +1,5 @@
 // orbx_lm.h -- device pieces shared by the Levenberg-Marquardt kernels (orbx_poseopt.hip,
-// orbx_optsim3.hip, orbx_localba.hip, orbx_essgraph.hip): Eigen's quaternion formulas, g2o's
+// orbx_optsim3.hip, orbx_localba.hip, orbx_globalba.hip, orbx_essgraph.hip): Eigen's quaternion formulas, g2o's
 // SE3Quat and Huber
 // kernel, the fixed-shape workgroup sums and the dense LDL^T of linear_solver_dense.h, for a
 // compile-time dimension per thread and for a run-time dimension per workgroup.  Everything is

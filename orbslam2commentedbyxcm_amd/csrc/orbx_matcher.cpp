@@ -2307,6 +2307,158 @@ int orbx_local_bundle_adjustment(orbx_matcher* m, const orbx_local_ba_batch* q) 
     return ORBX_OK;
 }
 
+static const char* global_ba_check(const orbx_global_ba_batch* q) {
+    if (q->batch < 0 || q->n_kf < 0 || q->n_pt < 0 || q->n_obs < 0 || q->n_slots < 0 || q->cap <= 0 ||
+        q->nlevels < 1 || q->nlevels > ORBX_MAX_LEVELS || q->iterations < 0 || q->max_env_blocks < 0)
+        return "bad argument";
+    if (!q->inv_level_sigma2) return "null host array";
+    if (q->batch == 0) return nullptr;
+    if (!q->kf_off || !q->pt_off || !q->obs_off || !q->status) return "null buffer";
+    if (q->n_kf > 0 && (!q->kf_Tcw || !q->kf_fixed || !q->kf_slot || !q->kf_Tcw_opt)) return "null keyframe table";
+    if (q->n_pt > 0 && (!q->pt_pos || !q->pt_pos_opt || !q->pt_included)) return "null point table";
+    if (q->n_obs > 0 && (!q->obs_kf || !q->obs_kp || !q->kps)) return "null observation table";
+    if (q->n_kf >= (1 << 24) || q->n_pt >= (1 << 26) || q->n_obs >= (1 << 26)) return "table too large";
+    if ((size_t)q->n_slots * (size_t)q->cap >= ((size_t)1 << 31)) return "n_slots x cap of 2^31 or more";
+    if (q->max_env_blocks >= ((int64_t)1 << 31) / q->batch) return "batch x max_env_blocks of 2^31 or more";
+    return nullptr;
+}
+
+// Optimizer::BundleAdjustment for a batch of maps in HBM (see include/orbx.h)
+int orbx_global_bundle_adjustment_batch_device(orbx_matcher* m, const orbx_global_ba_batch* q, void* stream) {
+    if (!m || !q) return fail(ORBX_ERR_ARG, "null argument");
+    if (const char* why = global_ba_check(q)) return fail(ORBX_ERR_ARG, why);
+    const int B = q->batch;
+    if (B == 0) return ORBX_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+    HIP_TRY(m->pscr.reserve(global_ba_workspace_bytes(B, q->n_kf, q->n_pt, q->n_obs, q->max_env_blocks), s));
+    GlobalBaArgs A{};
+    A.kf_off = q->kf_off;
+    A.n_kf = q->n_kf;
+    A.kf_Tcw = q->kf_Tcw;
+    A.kf_fixed = q->kf_fixed;
+    A.kf_slot = q->kf_slot;
+    A.pt_off = q->pt_off;
+    A.n_pt = q->n_pt;
+    A.pt_pos = q->pt_pos;
+    A.obs_off = q->obs_off;
+    A.n_obs = q->n_obs;
+    A.obs_kf = q->obs_kf;
+    A.obs_kp = q->obs_kp;
+    A.n_slots = q->n_slots;
+    A.cap = q->cap;
+    A.kps = q->kps;
+    A.u_right = q->u_right;
+    for (int l = 0; l < q->nlevels; l++) A.inv_sigma2[l] = q->inv_level_sigma2[l];
+    A.nlevels = q->nlevels;
+    A.fx = q->fx;
+    A.fy = q->fy;
+    A.cx = q->cx;
+    A.cy = q->cy;
+    A.bf = q->bf;
+    A.delta_mono = (float)std::sqrt(5.99);     // Optimizer.cc:115
+    A.delta_stereo = (float)std::sqrt(7.815);  // Optimizer.cc:116
+    A.iterations = q->iterations;
+    A.robust = q->robust;
+    A.dense = q->dense;
+    A.max_env_blocks = q->max_env_blocks;
+    A.kf_Tcw_out = q->kf_Tcw_opt;
+    A.pt_pos_out = q->pt_pos_opt;
+    A.pt_included = q->pt_included;
+    A.trace = q->trace;
+    A.chi2 = q->chi2;
+    A.status = q->status;
+    HIP_TRY(launch_global_ba(A, B, m->pscr.p, s));
+    return ORBX_OK;
+}
+
+// The single-problem host form: one staged problem, the batch kernel, one synchronisation.
+int orbx_global_bundle_adjustment(orbx_matcher* m, const orbx_global_ba_batch* q) {
+    if (!m || !q) return fail(ORBX_ERR_ARG, "null argument");
+    if (q->batch != 1) return fail(ORBX_ERR_ARG, "the host form takes one problem");
+    if (const char* why = global_ba_check(q)) return fail(ORBX_ERR_ARG, why);
+    if (q->kf_off[0] != 0 || q->kf_off[1] != q->n_kf || q->pt_off[0] != 0 || q->pt_off[1] != q->n_pt)
+        return fail(ORBX_ERR_ARG, "the host form's offsets are {0, n_kf} and {0, n_pt}");
+    if (q->n_pt > 0 && (q->obs_off[0] != 0 || q->obs_off[q->n_pt] != q->n_obs))
+        return fail(ORBX_ERR_ARG, "obs_off does not span the observations");
+    CallClock clock(m);
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    const size_t nk = (size_t)q->n_kf, np = (size_t)q->n_pt, no = (size_t)q->n_obs;
+    const size_t ck = nk ? nk : 1, cp = np ? np : 1, co = no ? no : 1;
+    const size_t nkp = (size_t)q->n_slots * (size_t)q->cap, ckp = nkp ? nkp : 1;
+    struct {
+        int32_t kf_off[2], pt_off[2];
+    } in{{0, q->n_kf}, {0, q->n_pt}}, *d_in = nullptr;
+    const int32_t zero = 0;
+    orbx_global_ba_batch d = *q;
+    HostStage st(pad);
+    st.out(&d.status, &q->status, 1, 1);
+    st.out(&d.trace, &q->trace, 2, 2);
+    st.out(&d.chi2, &q->chi2, 2, 2);
+    st.out(&d.kf_Tcw_opt, &q->kf_Tcw_opt, 12 * nk, 12 * ck);
+    st.out(&d.pt_pos_opt, &q->pt_pos_opt, 3 * np, 3 * cp);
+    st.out(&d.pt_included, &q->pt_included, np, cp);
+    st.in(&d.kf_Tcw, q->kf_Tcw, 12 * nk, 12 * ck);
+    st.in(&d.kf_fixed, q->kf_fixed, nk, ck);
+    st.in(&d.kf_slot, q->kf_slot, nk, ck);
+    st.in(&d.pt_pos, q->pt_pos, 3 * np, 3 * cp);
+    st.in(&d.obs_off, np ? (const void*)q->obs_off : (const void*)&zero, np + 1, cp + 1);
+    st.in(&d.obs_kf, q->obs_kf, no, co);
+    st.in(&d.obs_kp, q->obs_kp, no, co);
+    st.in(&d.kps, q->kps, nkp, ckp);
+    st.in_optional(&d.u_right, q->u_right, nkp, ckp);
+    st.in(&d_in, &in, 1, 1);
+    HIP_TRY(st.stage(m->pstage, s));
+    d.kf_off = d_in->kf_off;
+    d.pt_off = d_in->pt_off;
+    const int rc = orbx_global_bundle_adjustment_batch_device(m, &d, s);
+    if (rc) return rc;
+    HIP_TRY(st.download(s));
+    return ORBX_OK;
+}
+
+// A problem's envelope blocks (see include/orbx.h)
+int orbx_global_ba_envelope(int n_kf, const uint8_t* kf_fixed, int n_pt, const int32_t* obs_off,
+                            const int32_t* obs_kf, int n_obs, int64_t* blocks) {
+    if (n_kf < 0 || n_pt < 0 || n_obs < 0 || !blocks || (n_kf > 0 && !kf_fixed) || (n_pt > 0 && !obs_off) ||
+        (n_obs > 0 && !obs_kf))
+        return fail(ORBX_ERR_ARG, "bad argument");
+    auto range = [&](int j, int& o0, int& o1) {
+        o0 = std::min(std::max(obs_off[j], 0), n_obs);
+        o1 = std::min(std::max(obs_off[j + 1], o0), n_obs);
+    };
+    auto edge = [&](int o) { return obs_kf[o] >= 0 && obs_kf[o] < n_kf; };
+    std::vector<int32_t> idx((size_t)n_kf, -1), first;
+    std::vector<char> has((size_t)n_kf, 0);
+    int o0, o1;
+    for (int j = 0; j < n_pt; j++) {
+        range(j, o0, o1);
+        for (int o = o0; o < o1; o++)
+            if (edge(o)) has[(size_t)obs_kf[o]] = 1;
+    }
+    int F = 0;
+    for (int k = 0; k < n_kf; k++)
+        if (!kf_fixed[k] && has[(size_t)k]) idx[(size_t)k] = F++;
+    first.resize((size_t)F);
+    for (int f = 0; f < F; f++) first[(size_t)f] = f;
+    for (int j = 0; j < n_pt; j++) {
+        range(j, o0, o1);
+        int32_t lo = F;
+        for (int o = o0; o < o1; o++)
+            if (edge(o) && idx[(size_t)obs_kf[o]] >= 0) lo = std::min(lo, idx[(size_t)obs_kf[o]]);
+        for (int o = o0; o < o1; o++)
+            if (edge(o) && idx[(size_t)obs_kf[o]] >= 0) {
+                int32_t& fm = first[(size_t)idx[(size_t)obs_kf[o]]];
+                fm = std::min(fm, lo);
+            }
+    }
+    int64_t n = 0;
+    for (int f = 0; f < F; f++) n += f - first[(size_t)f] + 1;
+    *blocks = n;
+    return ORBX_OK;
+}
+
 static const char* essential_graph_check(const orbx_essential_graph_batch* q) {
     if (q->batch < 0 || q->n_kf < 0 || q->n_corr < 0 || q->n_edges < 0 || q->n_pt < 0 || q->iterations < 0 ||
         q->max_env_blocks < 0)

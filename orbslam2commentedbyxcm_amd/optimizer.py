@@ -1,6 +1,7 @@
-"""Optimizer::PoseOptimization, Optimizer::OptimizeSim3, Optimizer::LocalBundleAdjustment and
-Optimizer::OptimizeEssentialGraph on the GPU (include/orbx.h, csrc/orbx_poseopt.hip,
-csrc/orbx_optsim3.hip, csrc/orbx_localba.hip, csrc/orbx_essgraph.hip).
+"""Optimizer::PoseOptimization, Optimizer::OptimizeSim3, Optimizer::LocalBundleAdjustment,
+Optimizer::BundleAdjustment and Optimizer::OptimizeEssentialGraph on the GPU (include/orbx.h,
+csrc/orbx_poseopt.hip, csrc/orbx_optsim3.hip, csrc/orbx_localba.hip, csrc/orbx_globalba.hip,
+csrc/orbx_essgraph.hip).
 
 PoseOptimizer mirrors the one g2o call on ORB-SLAM2's per-frame path
 (src/Optimizer.cc:299-502): PoseOptimization for one frame on host arrays, and
@@ -9,7 +10,10 @@ pose_optimization_batch_device for B frames in HBM with the callers' epilogue
 (src/Optimizer.cc:1173-1358): OptimizeSim3 for one loop candidate on host arrays, and
 optimize_sim3_batch_device for B candidates in HBM.  LocalBundleAdjuster mirrors the one of
 LocalMapping::Run (src/Optimizer.cc:586-853): LocalBundleAdjustment for one local map on host
-arrays, and local_ba_batch_device for B local maps in HBM.  EssentialGraphOptimizer mirrors the
+arrays, and local_ba_batch_device for B local maps in HBM.  GlobalBundleAdjuster mirrors the
+one of Tracking::CreateInitialMapMonocular and LoopClosing::RunGlobalBundleAdjustment
+(src/Optimizer.cc:41-281): BundleAdjustment for one map on host arrays, and
+global_ba_batch_device for B maps in HBM.  EssentialGraphOptimizer mirrors the
 one of LoopClosing::CorrectLoop (src/Optimizer.cc:873-1150): OptimizeEssentialGraph for one map
 on host arrays, and essential_graph_batch_device for B maps in HBM; essential_graph_edges
 writes the graph's edges in the reference's order on the host.
@@ -358,6 +362,98 @@ class LocalBundleAdjuster(PoseOptimizer):
         q.n_erase, q.trace, q.status = ptr(d_n_erase), ptr(d_trace), ptr(d_status)
         s = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
         L.check(L.lib().orbx_local_bundle_adjustment_batch_device(self._h, C.byref(q), s))
+
+
+def global_ba_envelope(kf_fixed, obs_off, obs_kf) -> int:
+    """orbx_global_ba_envelope: the 6 x 6 blocks of one problem's envelope (max_env_blocks)."""
+    fixed = np.ascontiguousarray(kf_fixed, dtype=np.uint8)
+    off = np.ascontiguousarray(obs_off, dtype=np.int32)
+    okf = np.ascontiguousarray(obs_kf, dtype=np.int32)
+    ptr = lambda a: C.c_void_p(a.ctypes.data) if len(a) else None  # noqa: E731
+    n = C.c_int64(0)
+    L.check(L.lib().orbx_global_ba_envelope(len(fixed), ptr(fixed), max(len(off) - 1, 0), ptr(off), ptr(okf), len(okf),
+                                            C.byref(n)))
+    return int(n.value)
+
+
+class GlobalBundleAdjuster(PoseOptimizer):
+    """Optimizer::BundleAdjustment / GlobalBundleAdjustemnt (src/Optimizer.cc:41-281) on the GPU
+    (csrc/orbx_globalba.hip): BundleAdjustment for one map on host arrays and
+    global_ba_batch_device for B maps in HBM.  Which keyframes and points are good, where the
+    results go (SetPose or mTcwGBA) and the propagation after a loop's GBA stay with the caller;
+    the stop flag is not supported.  The handle, close() and last_call_us() are PoseOptimizer's."""
+
+    global_ba_envelope = staticmethod(global_ba_envelope)
+
+    def BundleAdjustment(self, kf_Tcw, kf_fixed, kf_slot, pt_pos, obs_off, obs_kf, obs_kp, keys_un, u_right,
+                         inv_level_sigma2, fx, fy, cx, cy, bf, iterations: int = 5, robust: bool = True,
+                         max_env_blocks: int | None = None, dense: bool = False) -> dict:
+        """One map on host arrays, the tables of LocalBundleAdjuster.LocalBundleAdjustment;
+        kf_fixed: mnId == 0.  iterations / robust: nIterations (the reference's default 5;
+        0: 10) / bRobust.  max_env_blocks None: what the problem needs.  Returns Tcw (K, 12)
+        and pos (P, 3) f32, pt_included (P,) u8, trace (2,) i32, chi2 (2,) f64 and status."""
+        T = _f32(kf_Tcw).reshape(-1, 12)
+        fixed = np.ascontiguousarray(kf_fixed, dtype=np.uint8)
+        slot = np.ascontiguousarray(kf_slot, dtype=np.int32)
+        pos = _f32(pt_pos).reshape(-1, 3)
+        off = np.ascontiguousarray(obs_off, dtype=np.int32)
+        okf = np.ascontiguousarray(obs_kf, dtype=np.int32)
+        okp = np.ascontiguousarray(obs_kp, dtype=np.int32)
+        keys = np.ascontiguousarray(keys_un, dtype=L.KEYPOINT_DTYPE)
+        if keys.ndim != 2:
+            raise ValueError("keys_un must be (n_slots, cap)")
+        ur = None if u_right is None else _f32(u_right)
+        K, P, no = len(T), len(pos), len(okf)
+        if len(fixed) != K or len(slot) != K or len(off) != P + 1 or len(okp) != no or \
+                (ur is not None and ur.shape != keys.shape):
+            raise ValueError("table sizes differ")
+        if max_env_blocks is None:
+            max_env_blocks = K * (K + 1) // 2 if dense else global_ba_envelope(fixed, off, okf)
+        sig = _f32(inv_level_sigma2)
+        kf_off = np.array([0, K], np.int32)
+        pt_off = np.array([0, P], np.int32)
+        out = dict(Tcw=np.zeros((K, 12), np.float32), pos=np.zeros((P, 3), np.float32),
+                   pt_included=np.zeros(P, np.uint8), trace=np.zeros(2, np.int32), chi2=np.zeros(2))
+        status = np.zeros(1, np.int32)
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+        q = L.GlobalBaBatch()
+        q.batch = 1
+        q.kf_off, q.n_kf, q.kf_Tcw, q.kf_fixed, q.kf_slot = ptr(kf_off), K, ptr(T), ptr(fixed), ptr(slot)
+        q.pt_off, q.n_pt, q.pt_pos = ptr(pt_off), P, ptr(pos)
+        q.obs_off, q.n_obs, q.obs_kf, q.obs_kp = ptr(off), no, ptr(okf), ptr(okp)
+        q.n_slots, q.cap, q.kps, q.u_right = keys.shape[0], keys.shape[1], ptr(keys), ptr(ur)
+        q.inv_level_sigma2, q.nlevels = sig.ctypes.data_as(F32P), len(sig)
+        q.fx, q.fy, q.cx, q.cy, q.bf = fx, fy, cx, cy, bf
+        q.iterations, q.robust, q.max_env_blocks, q.dense = int(iterations), int(bool(robust)), int(max_env_blocks), int(dense)
+        q.kf_Tcw_opt, q.pt_pos_opt, q.pt_included = ptr(out["Tcw"]), ptr(out["pos"]), ptr(out["pt_included"])
+        q.trace, q.chi2, q.status = ptr(out["trace"]), ptr(out["chi2"]), ptr(status)
+        L.check(L.lib().orbx_global_bundle_adjustment(self._h, C.byref(q)))
+        out["status"] = int(status[0])
+        return out
+
+    def global_ba_batch_device(self, d_kf_off, d_kf_Tcw, d_kf_fixed, d_kf_slot, d_pt_off, d_pt_pos, d_obs_off, d_obs_kf,
+                               d_obs_kp, d_kps, d_u_right, inv_level_sigma2, fx, fy, cx, cy, bf, iterations: int,
+                               robust: bool, max_env_blocks: int, d_kf_Tcw_opt, d_pt_pos_opt, d_pt_included, d_status,
+                               d_trace=None, d_chi2=None, dense: bool = False, stream=None) -> None:
+        """orbx_global_bundle_adjustment_batch_device on device tensors: the tables of
+        local_ba_batch_device, d_pt_included (n_pt,) u8, d_status (B,) i32, d_trace (B, 2) i32,
+        d_chi2 (B, 2) f64.  Asynchronous on `stream` (or the handle's)."""
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        sig = _f32(inv_level_sigma2)
+        q = L.GlobalBaBatch()
+        q.batch = int(d_kf_off.shape[0]) - 1
+        q.kf_off, q.n_kf, q.kf_Tcw = ptr(d_kf_off), int(d_kf_Tcw.shape[0]), ptr(d_kf_Tcw)
+        q.kf_fixed, q.kf_slot = ptr(d_kf_fixed), ptr(d_kf_slot)
+        q.pt_off, q.n_pt, q.pt_pos = ptr(d_pt_off), int(d_pt_pos.shape[0]), ptr(d_pt_pos)
+        q.obs_off, q.n_obs, q.obs_kf, q.obs_kp = ptr(d_obs_off), int(d_obs_kf.shape[0]), ptr(d_obs_kf), ptr(d_obs_kp)
+        q.n_slots, q.cap, q.kps, q.u_right = int(d_kps.shape[0]), int(d_kps.shape[1]), ptr(d_kps), ptr(d_u_right)
+        q.inv_level_sigma2, q.nlevels = sig.ctypes.data_as(F32P), len(sig)
+        q.fx, q.fy, q.cx, q.cy, q.bf = fx, fy, cx, cy, bf
+        q.iterations, q.robust, q.max_env_blocks, q.dense = int(iterations), int(bool(robust)), int(max_env_blocks), int(dense)
+        q.kf_Tcw_opt, q.pt_pos_opt, q.pt_included = ptr(d_kf_Tcw_opt), ptr(d_pt_pos_opt), ptr(d_pt_included)
+        q.trace, q.chi2, q.status = ptr(d_trace), ptr(d_chi2), ptr(d_status)
+        s = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        L.check(L.lib().orbx_global_bundle_adjustment_batch_device(self._h, C.byref(q), s))
 
 
 def essential_graph_envelope(n_kf: int, fixed: int, edge_v) -> int:

@@ -1,0 +1,258 @@
+"""orbx_global_bundle_adjustment(_batch_device) on the GPU against tests/global_ba_model.py.
+
+Scenes (global_ba_model.SPECS): TUM1 intrinsics, points 3-8 m away, 1 px x scale noise, keyframe
+slots and keypoint rows dealt out of storage order.  The smallest at which each piece can go
+wrong: 1 fixed + 1 free keyframe with 6 points; the initial-map shape (1 + 1 keyframes, 60 and
+300 monocular points, 20 iterations, robust -- the scale gauge is held only by lambda, and the
+keyframe's edge list crosses 64 and 256); all-mono, all-stereo and mixed maps of 6 to 12
+keyframes at 10 iterations, robust and not, one with 10 % gross outliers; a point with one
+observation, one with none, a free keyframe without an edge and two fixed keyframes of which
+one is not the first; 255 / 256 / 257 edges; 1 and 257 points; banded loop maps with 63 / 64 /
+65 free keyframes (the local BA's cap and the wave boundary) and one of 257 keyframes at 2
+iterations.
+
+Every comparison first asserts the conditions on its scene (global_ba_model.guard): all
+variants of the model agree on the LM trace, the active sets, pt_included and the status, every
+LDL^T pivot is positive, and every LM decision value is farther from 0 than 1000 x its spread
+between the variants.  Then the flags, the trace and the status must equal the model's, and
+poses and positions lie within 8 x THAT SCENE's spread between the variants (python
+tests/global_ba_spread.py prints them), floor 2 float32 ulps of the entry.  The initial chi2
+depends on the inputs alone and is a sum of at most a few thousand positive doubles (1e-10
+relative is 1e5 roundings of it); the final chi2 gets 8 x its spread between the variants on top.
+"""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+import global_ba_model as G
+import local_ba_model as M
+
+pytestmark = pytest.mark.gpu
+
+
+def assert_guard(name):
+    sc, vs, (ok, why), sp = G.checked(name)
+    assert ok, (name, why)
+    return sc, vs[0], sp + (chi_spread(vs),)
+
+
+def chi_spread(vs):
+    c = np.array([v["chi2"][1] for v in vs])
+    return float(c.max() - c.min())
+
+
+@pytest.fixture(scope="module")
+def opt(orbx_built):
+    from orbslam2commentedbyxcm_amd.optimizer import GlobalBundleAdjuster
+    o = GlobalBundleAdjuster()
+    yield o
+    o.close()
+
+
+def keypoints(xy, octv):
+    from orbslam2commentedbyxcm_amd import _lib as L
+    k = np.zeros(xy.shape[:-1], L.KEYPOINT_DTYPE)
+    k["x"], k["y"], k["octave"] = xy[..., 0], xy[..., 1], octv
+    return k
+
+
+def run_batch(opt, scenes, iterations, robust, max_env_blocks=None, dense=False, trace=True, chi2=True):
+    import torch
+    A = G.batch_arrays(scenes)
+    B = len(scenes)
+    if max_env_blocks is None:
+        max_env_blocks = max(G.envelope_blocks(s, dense) for s in scenes)
+    dev = torch.device("cuda", opt.device)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    n_kf, n_pt = len(A["fixed"]), len(A["pos"])
+    kps = keypoints(A["kps_xy"], A["kps_oct"])
+    d_T = torch.full((n_kf, 12), float("nan"), dtype=torch.float32, device=dev)
+    d_X = torch.full((n_pt, 3), float("nan"), dtype=torch.float32, device=dev)
+    d_in = torch.full((n_pt,), 9, dtype=torch.uint8, device=dev)
+    d_st = torch.full((B,), -9, dtype=torch.int32, device=dev)
+    d_tr = torch.full((B, 2), -9, dtype=torch.int32, device=dev) if trace else None
+    d_c2 = torch.full((B, 2), float("nan"), dtype=torch.float64, device=dev) if chi2 else None
+    s0 = scenes[0]
+    fx, fy, cx, cy, bf = s0["cam"]
+    torch.cuda.synchronize(dev)
+    opt.global_ba_batch_device(
+        t(A["kf_off"]), t(A["Tcw"]), t(A["fixed"]), t(A["slot"]), t(A["pt_off"]), t(A["pos"]), t(A["obs_off"]),
+        t(A["obs_kf"]), t(A["obs_kp"]), t(kps.view(np.uint8).reshape(A["n_slots"], A["cap"] * 28)).view(A["n_slots"], A["cap"], 28),
+        t(A["u_right"]), s0["inv_sigma2"], fx, fy, cx, cy, bf, iterations, robust, max_env_blocks, d_T, d_X, d_in, d_st,
+        d_trace=d_tr, d_chi2=d_c2, dense=dense, stream=torch.cuda.current_stream(dev))
+    torch.cuda.synchronize(dev)
+    cpu = lambda x: None if x is None else x.cpu().numpy()  # noqa: E731
+    return dict(Tcw=cpu(d_T), pos=cpu(d_X), pt_included=cpu(d_in), status=cpu(d_st), trace=cpu(d_tr), chi2=cpu(d_c2),
+                arrays=A)
+
+
+def part(got, b):
+    """Problem b's rows of a batch result."""
+    A = got["arrays"]
+    k0, k1 = A["kf_off"][b:b + 2]
+    p0, p1 = A["pt_off"][b:b + 2]
+    return dict(Tcw=got["Tcw"][k0:k1], pos=got["pos"][p0:p1], pt_included=got["pt_included"][p0:p1],
+                status=int(got["status"][b]), trace=None if got["trace"] is None else got["trace"][b],
+                chi2=None if got["chi2"] is None else got["chi2"][b])
+
+
+def run_scene(opt, name, **kw):
+    sc, r, sp = assert_guard(name)
+    return part(run_batch(opt, [sc], **G.params(name), **kw), 0)
+
+
+def assert_close(got, want32, tol, what):
+    """8 x the scene's spread between the variants, floor 2 float32 ulps of the entry."""
+    lim = np.maximum(tol, 2 * np.spacing(np.abs(want32)).astype(np.float64))
+    diff = np.abs(got.astype(np.float64) - want32.astype(np.float64))
+    assert np.isfinite(got).all(), what
+    assert (diff <= lim).all(), (what, float(diff.max()), float((diff / lim).max()))
+
+
+def assert_problem(g, r, sp, what):
+    dT = np.abs(g["Tcw"].astype(np.float64) - r["Tcw"]).max() if g["Tcw"].size else 0.0
+    dX = np.abs(g["pos"].astype(np.float64) - r["pos"]).max() if g["pos"].size else 0.0
+    print(f"{what}: trace {None if g['trace'] is None else g['trace'].tolist()} model {r['trace'].tolist()} "
+          f"status {g['status']} chi2 {None if g['chi2'] is None else g['chi2'].tolist()} model {r['chi2'].tolist()} "
+          f"max |dT| {dT:.3g} (spread {sp[0]:.3g}) max |dX| {dX:.3g} (spread {sp[1]:.3g})")
+    assert g["status"] == r["status"], what
+    if g["trace"] is not None:
+        assert np.array_equal(g["trace"], r["trace"]), (what, g["trace"].tolist(), r["trace"].tolist())
+    assert np.array_equal(g["pt_included"], r["pt_included"]), what
+    if g["chi2"] is not None:
+        lim = 1e-10 * np.abs(r["chi2"]) + np.array([0.0, 8 * sp[2]])
+        assert (np.abs(g["chi2"] - r["chi2"]) <= lim).all(), (what, g["chi2"].tolist(), r["chi2"].tolist())
+    assert_close(g["Tcw"], r["Tcw"], 8 * sp[0], what + " poses")
+    assert_close(g["pos"], r["pos"], 8 * sp[1], what + " positions")
+
+
+@pytest.mark.parametrize("name", list(G.SPECS))
+def test_single_problem_batch_equals_model(opt, name):
+    sc, r, sp = assert_guard(name)
+    g = part(run_batch(opt, [sc], **G.params(name)), 0)
+    assert_problem(g, r, sp, name)
+    out = g["pt_included"] == 0
+    assert g["pos"][out].tobytes() == sc["pos"][out].tobytes()
+
+
+def test_scenes_are_what_their_names_say():
+    for n in (255, 256, 257):
+        assert len(G.scene(f"edges-{n}")["obs_kf"]) == n
+    for name, free in (("banded-63", 63), ("banded-64", 64), ("banded-65", 65), ("banded-257", 256)):
+        sc, r, _ = assert_guard(name)
+        assert len(r["active_kf"][0]) == free and r["blocks"] < free * (free + 1) // 4
+    sc, r, _ = assert_guard("init-300")
+    assert len(sc["obs_kf"]) == 600 and (np.bincount(sc["obs_kf"]) == 300).all() and sc["u_right"] is None
+    assert G.params("init-60") == dict(iterations=20, robust=True)
+    assert len(assert_guard("pts-1")[0]["pos"]) == 1 and len(assert_guard("pts-257")[0]["pos"]) == 257
+    assert assert_guard("mixed-out10")[0]["gross"].mean() > 0.05
+    kinds = {G.SPECS[n][1].get("kind", "mixed") for n in ("mono", "stereo", "mixed")}
+    assert kinds == {"mono", "stereo", "mixed"}
+    assert {G.SPECS[n][3] for n in ("mono", "stereo", "mixed", "mixed-out10")} == {True, False}
+    rejected = [n for n in G.SPECS if assert_guard(n)[1]["trace"][1] > assert_guard(n)[1]["trace"][0]]
+    assert rejected                                                     # some scene rejects a trial
+
+
+@pytest.mark.parametrize("name", G.BANDED)
+def test_dense_switch_gives_the_envelope_runs_bytes(opt, name):
+    sc, r, sp = assert_guard(name)
+    g = run_scene(opt, name)
+    d = run_scene(opt, name, dense=True)
+    for k in ("Tcw", "pos", "pt_included", "trace", "chi2"):
+        assert g[k].tobytes() == d[k].tobytes(), (name, k)
+    assert g["status"] == d["status"] == 0
+
+
+BATCH8 = ("mixed", "1+1-6pts", "banded-65", "mixed-out10", "odd", "edges-257", "stereo", "init-60")
+
+
+def test_batch_of_8_equals_each_alone_and_itself_twice(opt):
+    """One launch takes one iterations / robust pair: the eight scenes run at 10 iterations,
+    robust, which is not every scene's own pair -- so the comparison is with each alone under
+    the same pair (bytes), and with the model where the pair is the scene's own."""
+    scenes = [assert_guard(n) for n in BATCH8]
+    kw = dict(iterations=10, robust=True)
+    got = run_batch(opt, [s for s, _, _ in scenes], **kw)
+    again = run_batch(opt, [s for s, _, _ in scenes], **kw)
+    for k in ("Tcw", "pos", "pt_included", "status", "trace", "chi2"):
+        assert got[k].tobytes() == again[k].tobytes(), k
+    for b, (name, (sc, r, sp)) in enumerate(zip(BATCH8, scenes)):
+        g = part(got, b)
+        if G.params(name) == kw:
+            assert_problem(g, r, sp, f"batch8[{b}] {name}")
+        alone = part(run_batch(opt, [sc], max_env_blocks=G.envelope_blocks(sc), **kw), 0)
+        for k in ("Tcw", "pos", "pt_included", "trace", "chi2"):
+            assert g[k].tobytes() == alone[k].tobytes(), (name, k)
+        assert g["status"] == alone["status"], name
+
+
+def test_optional_outputs_may_be_null(opt):
+    sc, r, sp = assert_guard("mixed")
+    g = run_scene(opt, "mixed", trace=False, chi2=False)
+    assert_problem(g, r, sp, "no trace, no chi2")
+
+
+def host_call(opt, sc, **kw):
+    fx, fy, cx, cy, bf = sc["cam"]
+    return opt.BundleAdjustment(sc["Tcw"], sc["fixed"], sc["slot"], sc["pos"], sc["obs_off"], sc["obs_kf"],
+                                sc["obs_kp"], keypoints(sc["kps_xy"], sc["kps_oct"]), sc["u_right"],
+                                sc["inv_sigma2"], fx, fy, cx, cy, bf, **kw)
+
+
+@pytest.mark.parametrize("name", ["1+1-6pts", "init-60", "odd", "mixed-out10", "banded-64", "pts-1"])
+def test_single_host_call_equals_batch_bytes(opt, name):
+    sc, r, sp = assert_guard(name)
+    g = run_scene(opt, name)
+    h = host_call(opt, sc, **G.params(name))
+    for k in ("Tcw", "pos", "pt_included", "trace", "chi2"):
+        assert h[k].tobytes() == g[k].tobytes(), (name, k)
+    assert h["status"] == g["status"]
+    assert opt.last_call_us() > 0
+
+
+def test_no_free_keyframe_capacity_and_bad_indices(opt):
+    none = M.make_scene(0, n_free=0, n_fixed=3, n_pts=12)
+    g = part(run_batch(opt, [none], 10, True, max_env_blocks=4), 0)
+    assert g["status"] == G.STATUS_NO_FREE_KF and not g["trace"].any() and not g["chi2"].any()
+    assert g["Tcw"].tobytes() == none["Tcw"].tobytes() and g["pos"].tobytes() == none["pos"].tobytes()
+    assert not g["pt_included"].any()
+    h = host_call(opt, none)
+    assert h["status"] == G.STATUS_NO_FREE_KF and h["Tcw"].tobytes() == none["Tcw"].tobytes()
+
+    sc, r, sp = assert_guard("banded-63")
+    g = run_scene(opt, "banded-63", max_env_blocks=r["blocks"] - 1)     # one block too small
+    assert g["status"] == G.STATUS_CAPACITY and not g["trace"].any() and not g["pt_included"].any()
+    assert g["Tcw"].tobytes() == sc["Tcw"].tobytes() and g["pos"].tobytes() == sc["pos"].tobytes()
+    assert run_scene(opt, "banded-63", max_env_blocks=r["blocks"])["status"] == 0
+
+    sc = dict(G.scene("mixed"))
+    kf, kp = sc["obs_kf"].copy(), sc["obs_kp"].copy()
+    kf[3], kp[7], kf[11] = len(sc["fixed"]), sc["kps_xy"].shape[1], -1
+    o0 = sc["obs_off"][5]
+    kf[o0 + 1] = kf[o0]                                                 # a keyframe twice in one point
+    sc["obs_kf"], sc["obs_kp"] = kf, kp
+    vs = G.variants(sc, **G.params("mixed"))
+    ok, why = G.guard(vs)
+    assert ok, why
+    assert vs[0]["status"] == G.STATUS_BAD_INDEX
+    g = part(run_batch(opt, [sc], **G.params("mixed")), 0)
+    assert_problem(g, vs[0], G.spread(vs) + (chi_spread(vs),), "bad indices")
+
+
+def test_all_stereo_robust_walks_the_local_bas_first_phase(opt):
+    """On an all-stereo map the deltas of the two kernels coincide (sqrt(7.815)), so
+    BundleAdjustment(5 iterations, robust) and the first optimisation of LocalBundleAdjustment
+    must walk the same LM path: the same iterations and solves."""
+    from orbslam2commentedbyxcm_amd.optimizer import LocalBundleAdjuster
+    sc, r, sp = assert_guard("stereo")
+    g = host_call(opt, sc, iterations=5, robust=True)
+    lba = LocalBundleAdjuster(matcher=opt)
+    fx, fy, cx, cy, bf = sc["cam"]
+    l = lba.LocalBundleAdjustment(sc["Tcw"], sc["fixed"], sc["slot"], sc["pos"], sc["obs_off"], sc["obs_kf"],
+                                  sc["obs_kp"], keypoints(sc["kps_xy"], sc["kps_oct"]), sc["u_right"],
+                                  sc["inv_sigma2"], fx, fy, cx, cy, bf)
+    assert g["status"] == 0 and l["status"] == 0
+    assert g["trace"].tolist() == l["trace"][0].tolist() and g["trace"][0] > 0
+    m = G.global_ba(sc, iterations=5, robust=True)
+    assert g["trace"].tolist() == m["trace"].tolist()
