@@ -1216,8 +1216,9 @@ int orbx_optimize_sim3(orbx_matcher* m, const orbx_optimize_sim3_batch* os);
  * quadratic form of BaseBinaryEdge, RobustKernelHuber, SE3Quat), for B local maps in HBM in one
  * launch: one persistent workgroup per problem runs optimize(5), the chi2 / depth test,
  * optimize(10) on the edges that passed and the final test.  The covisibility walk that
- * chooses the keyframes and points (cc:526-583) stays with the caller, as do the erasure of
- * the flagged observations and UpdateNormalAndDepth (cc:828-853).  The stop flag (pbStopFlag)
+ * chooses the keyframes and points (cc:526-583) stays with the caller (or with
+ * orbx_local_ba_assemble_device on a covisibility graph), as do the erasure of the flagged
+ * observations (orbx_local_ba_apply_device) and UpdateNormalAndDepth (cc:828-853).  The stop flag (pbStopFlag)
  * is not supported: bDoMore is always true.  Float inputs are widened to double, everything
  * after is double (but the two float intermediates of the stereo projection), outputs are
  * rounded to float once.  Every sum has a fixed shape (no floating-point atomics) and no
@@ -1664,12 +1665,182 @@ int orbx_initializer_initialize(orbx_initializer* s, const orbx_initializer_batc
  * reproduced, later ones restart the sequence.  Host only, no GPU. */
 int orbx_initializer_sets(int32_t* sets, int n, int iterations);
 
+/* ---- The covisibility graph: MapPoint observations, KeyFrame::UpdateConnections ----
+ * A device-resident covisibility graph over keyframe ids 0 .. max_keyframes - 1 (DESIGN.md
+ * §4.24).  The map it reads is the caller's, by device pointer: kf_mp [n_keyframes][cap] =
+ * mvpMapPoints as MapPoint ids (-1 = NULL; an id outside [0, n_mappoints) counts as NULL),
+ * kf_n [n_keyframes] the rows' lengths (clamped into [0, cap]), kf_bad [n_keyframes] /
+ * mp_bad [n_mappoints] = isBad() or NULL.  The keyframe id stands in for the reference's
+ * KeyFrame* wherever its order is a pointer order (std::map<KeyFrame*, ...>).  All integer
+ * work: results are exact and do not depend on scheduling.
+ *
+ * orbx_covis_refresh_observations_device builds MapPoint::GetObservations() for every MapPoint
+ * as a CSR: point p owns obs_off[p] .. obs_off[p + 1] of obs_kf / obs_idx, ascending keyframe
+ * id.  Rows of bad keyframes contribute nothing (SetBadFlag erased their observations).  Where a
+ * row names one MapPoint at several indices the lowest index holds the observation, the others
+ * count as NULL in every later call (the cleaned copy of the table, `mp` of the view) and the
+ * keyframe's status gets ORBX_COVIS_STATUS_DUPLICATE (rewritten by every refresh).  The graph
+ * keeps kf_n, kf_bad and mp_bad and reads them in the later calls; it reads kf_mp only here, so
+ * a change of the table takes effect with the next refresh.
+ *
+ * orbx_covis_update_connections_device is KeyFrame::UpdateConnections (KeyFrame.cc:324-415)
+ * for the Q keyframes ids[0 .. Q) (a host array), with the result of calling it on ids[0],
+ * ids[1], ... in order: the row mConnectedKeyFrameWeights (ascending id, entries below the
+ * threshold of 15 included), mvpOrderedConnectedKeyFrames / mvOrderedWeights (weight descending,
+ * id descending among equal weights; the entries >= 15, or pKFmax alone -- the lowest id among
+ * the maxima -- when there is none), mbFirstConnection and mpParent (the list's front, set once,
+ * never for id 0).  An empty counter leaves the keyframe untouched.  AddConnection
+ * (cc:139-153) on the connected keyframes inserts or overwrites one entry of their rows and,
+ * only when the entry is new or its weight differs, re-orders their whole row, entries below
+ * 15 included (UpdateBestCovisibles, cc:160-182).  A bad keyframe among ids is skipped with
+ * ORBX_COVIS_STATUS_BAD_KEYFRAME; a row of more than max_conn entries, the keyframe's own or
+ * one that a message would grow, sets ORBX_COVIS_STATUS_CAPACITY and leaves that keyframe's
+ * state untouched (all of a batch's messages to it are then dropped).  A repeated id is ORBX_ERR_ARG.  The status bits but DUPLICATE are sticky.
+ *
+ * orbx_covis_erase_keyframe_device is the connection part of SetBadFlag (cc:506-508, 519-520):
+ * EraseConnection(id) on every keyframe of id's row, each re-ordered if it held the entry, then
+ * id's row and list are cleared.  Id 0 is a no-op.  mbNotErase, the children's new parents and
+ * EraseObservation stay with the caller, who sets kf_bad and refreshes the observations.
+ *
+ * Rows in LDS: one workgroup counts a keyframe's connections in an LDS histogram while
+ * max_keyframes <= ORBX_COVIS_LDS_KEYFRAMES (orbx_debug_set "covis_lds_keyframes" lowers the
+ * bound for graphs created afterwards), in a global row above it; the results are the same.
+ * ORBX_ERR_ARG, decided before any device call: a null graph or required pointer, a negative
+ * size, max_conn > ORBX_COVIS_MAX_CONN, cap > 8192, an id outside the graph, a repeated id.
+ * The calls are asynchronous on `stream` (or the graph's own); a call on another stream first
+ * waits for the last one. */
+typedef struct orbx_covis orbx_covis;
+#define ORBX_COVIS_MAX_CONN 8192
+#define ORBX_COVIS_LDS_KEYFRAMES 8192
+#define ORBX_COVIS_STATUS_CAPACITY 1
+#define ORBX_COVIS_STATUS_BAD_KEYFRAME 2
+#define ORBX_COVIS_STATUS_DUPLICATE 4
+int orbx_covis_create(int device, int max_keyframes, int cap, int max_mappoints, int max_conn, orbx_covis** out);
+void orbx_covis_destroy(orbx_covis* g);
+void* orbx_covis_stream(orbx_covis* g);
+int orbx_covis_refresh_observations_device(orbx_covis* g, int n_keyframes, const int32_t* kf_mp, const int32_t* kf_n,
+                                           const uint8_t* kf_bad, int n_mappoints, const uint8_t* mp_bad, void* stream);
+/* The host form: the map as host arrays, copied into the graph's own buffer (which then serves
+ * the later calls) on the graph's stream. */
+int orbx_covis_refresh_observations(orbx_covis* g, int n_keyframes, const int32_t* kf_mp, const int32_t* kf_n,
+                                    const uint8_t* kf_bad, int n_mappoints, const uint8_t* mp_bad);
+int orbx_covis_update_connections_device(orbx_covis* g, const int32_t* ids, int Q, void* stream);
+int orbx_covis_erase_keyframe_device(orbx_covis* g, int id, void* stream);
+
+/* The graph's arrays by device pointer, for the caller's own kernels (valid until the graph is
+ * destroyed; read them on the stream of the last call or after synchronising it). */
+typedef struct {
+    int max_keyframes, cap, max_mappoints, max_conn;
+    int n_keyframes, n_mappoints;   /* of the last refresh */
+    const int32_t* obs_off;         /* [n_mappoints + 1] */
+    const int32_t* obs_kf;          /* [obs_off[n_mappoints]] */
+    const int32_t* obs_idx;
+    const int32_t* mp;              /* [max_keyframes][cap] the cleaned copy of kf_mp */
+    const int32_t* row_kf;          /* [max_keyframes][max_conn] mConnectedKeyFrameWeights */
+    const int32_t* row_w;
+    const int32_t* row_n;           /* [max_keyframes] */
+    const int32_t* ordered_kf;      /* [max_keyframes][max_conn] mvpOrderedConnectedKeyFrames */
+    const int32_t* ordered_w;       /* mvOrderedWeights */
+    const int32_t* ordered_n;       /* [max_keyframes] */
+    const int32_t* parent;          /* [max_keyframes] mpParent, -1 = NULL */
+    const uint8_t* first;           /* [max_keyframes] mbFirstConnection */
+    const int32_t* status;          /* [max_keyframes] ORBX_COVIS_STATUS_* */
+} orbx_covis_view;
+int orbx_covis_view_device(orbx_covis* g, orbx_covis_view* view);
+/* Host convenience: waits for the graph's last call and copies `bytes` bytes of one of the
+ * view's arrays (from src, a device address) to the host. */
+int orbx_covis_read(orbx_covis* g, const void* src, void* dst, size_t bytes);
+
+/* GetBestCovisibilityKeyFrames(N) (cc:201-209) of every keyframe: out [max_keyframes][N] (-1
+ * behind the list's end), out_n [max_keyframes]; device pointers. */
+int orbx_covis_best_covisibles_device(orbx_covis* g, int N, int32_t* out, int32_t* out_n, void* stream);
+/* GetCovisiblesByWeight(w) (cc:212-229) of every keyframe: a prefix of the ordered list, its
+ * length in out_n [max_keyframes]; out [max_keyframes][max_conn] (-1 behind it) or NULL.  As
+ * the reference: upper_bound on the descending weights, and the explicit empty result only
+ * when the search reached the end and the last weight is below w. */
+int orbx_covis_covisibles_by_weight_device(orbx_covis* g, int w, int32_t* out, int32_t* out_n, void* stream);
+/* Host convenience: keyframe id's ordered list (what orbx_kfdb_set_covisibility takes): *n =
+ * its length, the first min(*n, cap) entries to kf and, unless NULL, w.  Synchronises. */
+int orbx_covis_ordered(orbx_covis* g, int id, int32_t* kf, int32_t* w, int cap, int* n);
+
+/* ---- Optimizer::LocalBundleAdjustment's graph assembly and write-back on the device ----
+ * orbx_local_ba_assemble_device runs Optimizer.cc:526-583 and the edge walk of cc:656-760 for
+ * B current keyframes cur_kf[0 .. B) (a host array) on the covisibility graph `g`, whose
+ * observations are those of the last refresh (refresh after kf_mp or a bad flag changed), and
+ * writes the tables of orbx_local_ba_batch:
+ *   keyframe rows of a problem: cur_kf, then its GetVectorCovisibleKeyFrames() in list order
+ *   without the bad ones (lLocalKeyFrames), then lFixedCameras in the order of the walk (points
+ *   in lLocalMapPoints order, each point's observers in ascending id); kf_fixed = 1 for the
+ *   fixed cameras and for id 0, kf_slot = kf_id = the keyframe id, kf_Tcw from kf_pose;
+ *   point rows: lLocalMapPoints in first-appearance order (the local keyframes in list order,
+ *   each one's row in index order; NULL, bad and later copies of a duplicate skipped), pt_pos
+ *   from mp_pos, pt_id the MapPoint id;
+ *   observations: per point its observers in ascending id as (row within the problem's
+ *   keyframe rows, keypoint index); obs_off is compact over the batch, obs_off[pt_off[B]] the
+ *   total.
+ * kf_off / pt_off [B + 1], counts [B][3] = {keyframe rows, point rows, observations} and status
+ * [B] are written on the device.  max_kf_rows / max_pt_rows / max_obs are the tables' capacities
+ * for the whole batch (obs_off holds max_pt_rows + 1): a problem that does not fit what the
+ * problems before it left gets empty ranges, zero counts and ORBX_LOCAL_BA_STATUS_CAPACITY; the
+ * others are laid out as if it were not there.  Nothing is read back: pass the capacities as
+ * n_kf / n_pt / n_obs of orbx_local_bundle_adjustment_batch_device, which clamps against them.
+ * Every pointer but cur_kf is a device pointer.  Asynchronous on `stream` (or the graph's). */
+typedef struct {
+    int batch;
+    const int32_t* cur_kf;     /* host [B] */
+    const float* kf_pose;      /* [max_keyframes][12] GetPose() rows 0..2, by keyframe id */
+    const float* mp_pos;       /* [n_mappoints][3] GetWorldPos(), by MapPoint id */
+    int max_kf_rows, max_pt_rows, max_obs;
+    int32_t* kf_off;           /* [B + 1] out */
+    float* kf_Tcw;             /* [max_kf_rows][12] out */
+    uint8_t* kf_fixed;         /* [max_kf_rows] out */
+    int32_t* kf_slot;          /* [max_kf_rows] out */
+    int32_t* kf_id;            /* [max_kf_rows] out */
+    int32_t* pt_off;           /* [B + 1] out */
+    float* pt_pos;             /* [max_pt_rows][3] out */
+    int32_t* pt_id;            /* [max_pt_rows] out */
+    int32_t* obs_off;          /* [max_pt_rows + 1] out */
+    int32_t* obs_kf;           /* [max_obs] out */
+    int32_t* obs_kp;           /* [max_obs] out */
+    int32_t* counts;           /* [B][3] out */
+    int32_t* status;           /* [B] out */
+} orbx_local_ba_assembly;
+int orbx_local_ba_assemble_device(orbx_covis* g, const orbx_local_ba_assembly* a, void* stream);
+
+/* The index part of Optimizer.cc:828-853 after orbx_local_bundle_adjustment_batch_device on the
+ * assembled tables: kf_Tcw_opt of the keyframes that are not fixed goes to kf_pose through
+ * kf_id, pt_pos_opt to mp_pos through pt_id, and for every erase[o] kf_mp[keyframe][keypoint]
+ * = -1 (EraseMapPointMatch; erase or kf_mp NULL: skipped).  What EraseObservation does to a
+ * point's nObs, reference keyframe and badness, and UpdateNormalAndDepth, stay with the caller.
+ * Device pointers; asynchronous on `stream` (or the graph's). */
+typedef struct {
+    int batch;
+    int max_kf_rows, max_pt_rows;   /* the tables' capacities, as assembled */
+    const int32_t* kf_off;
+    const int32_t* kf_id;
+    const uint8_t* kf_fixed;
+    const float* kf_Tcw_opt;
+    const int32_t* pt_off;
+    const int32_t* pt_id;
+    const float* pt_pos_opt;
+    const int32_t* obs_off;
+    const int32_t* obs_kf;
+    const int32_t* obs_kp;
+    const uint8_t* erase;           /* [n_obs] or NULL */
+    int n_keyframes, n_mappoints, cap;
+    float* kf_pose;                 /* [n_keyframes][12] in/out */
+    float* mp_pos;                  /* [n_mappoints][3] in/out */
+    int32_t* kf_mp;                 /* [n_keyframes][cap] in/out or NULL */
+} orbx_local_ba_apply;
+int orbx_local_ba_apply_device(orbx_covis* g, const orbx_local_ba_apply* a, void* stream);
+
 /* Alternative kernel forms and diagnostics switches, process-wide (tests and A/B tools;
  * the product reads no environment).  Names: "pz_seg" (pyramid levels per launch, 0 = one
  * launch), "pz_byte" (byte-read k_pyramid), "desc_tiles" (tile-major describe),
  * "extract_dma" (single host call through DMA copies), "replay_threads" (64..1024),
  * "dup_stage" (launch extraction stage k twice), "oct_stamps" / "call_stamps" /
- * "match_stamps" (phase stamps to stderr), "essgraph_stamps" (orbx_optimize_essential_graph*:
+ * "match_stamps" (phase stamps to stderr), "covis_lds_keyframes" (the covisibility graph's LDS
+ * bound, read by orbx_covis_create), "essgraph_stamps" (orbx_optimize_essential_graph*:
  * problem 0's wall-clock ticks in the linearisations and in the linear solves to stderr;
  * synchronises the stream).  value < 0 restores the default; name NULL
  * restores every default.  Every form gives the same results.  A frame size's plan reads

@@ -7,6 +7,7 @@
 // Errors throw orbx::Error on this side of the boundary; nothing throws across it.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <map>
 #include <set>
@@ -237,6 +238,75 @@ inline void ComputeStereoFromRGBD(const orbx_camera& cam, const std::vector<orbx
                                         mDepthMapFactor, mbf, mvKeysUn.data(), mvuRight.data(), mvDepth.data()));
 }
 
+// The covisibility graph (KeyFrame::UpdateConnections and the lists it keeps, src/KeyFrame.cc:
+// 139-229, 324-415, 506-520) over keyframe ids in [0, maxKeyFrames): a KeyFrame* is its mnId,
+// a MapPoint* its id.  The map is mvpMapPoints as a [keyframes][cap] id table (-1 = NULL).
+class Covisibility {
+public:
+    Covisibility(int maxKeyFrames, int cap, int maxMapPoints, int maxConnections = 256, int device = 0)
+        : maxConn_(maxConnections) {
+        check(orbx_covis_create(device, maxKeyFrames, cap, maxMapPoints, maxConnections, &h_));
+    }
+    ~Covisibility() { orbx_covis_destroy(h_); }
+    Covisibility(const Covisibility&) = delete;
+    Covisibility& operator=(const Covisibility&) = delete;
+
+    // MapPoint::GetObservations() of every point from the keyframes' mvpMapPoints: device
+    // tables (they must outlive the later calls) ...
+    void RefreshObservations(int nKeyFrames, const int32_t* d_kf_mp, const int32_t* d_kf_n, const uint8_t* d_kf_bad,
+                             int nMapPoints, const uint8_t* d_mp_bad, void* stream = nullptr) {
+        check(orbx_covis_refresh_observations_device(h_, nKeyFrames, d_kf_mp, d_kf_n, d_kf_bad, nMapPoints, d_mp_bad,
+                                                     stream));
+    }
+    // ... or host vectors (kfBad / mpBad may be empty: nothing is bad)
+    void RefreshObservations(const std::vector<int32_t>& kfMapPoints, const std::vector<int32_t>& kfN,
+                             const std::vector<uint8_t>& kfBad, int nMapPoints, const std::vector<uint8_t>& mpBad) {
+        check(orbx_covis_refresh_observations(h_, (int)kfN.size(), kfMapPoints.data(), kfN.data(),
+                                              kfBad.empty() ? nullptr : kfBad.data(), nMapPoints,
+                                              mpBad.empty() ? nullptr : mpBad.data()));
+    }
+    // pKF->UpdateConnections() for each of ids, in order
+    void UpdateConnections(const std::vector<int32_t>& ids, void* stream = nullptr) {
+        check(orbx_covis_update_connections_device(h_, ids.data(), (int)ids.size(), stream));
+    }
+    void UpdateConnections(int id) { UpdateConnections(std::vector<int32_t>{id}); }
+    // the connection part of pKF->SetBadFlag()
+    void EraseKeyFrame(int id, void* stream = nullptr) { check(orbx_covis_erase_keyframe_device(h_, id, stream)); }
+    // vector<KeyFrame*> GetVectorCovisibleKeyFrames(); weights: mvOrderedWeights
+    std::vector<int32_t> GetVectorCovisibleKeyFrames(int id, std::vector<int32_t>* weights = nullptr) {
+        std::vector<int32_t> kf((size_t)maxConn_), w((size_t)maxConn_);
+        int n = 0;
+        check(orbx_covis_ordered(h_, id, kf.data(), w.data(), maxConn_, &n));
+        kf.resize((size_t)n);
+        w.resize((size_t)n);
+        if (weights) *weights = w;
+        return kf;
+    }
+    std::vector<int32_t> GetBestCovisibilityKeyFrames(int id, int N) {
+        std::vector<int32_t> kf = GetVectorCovisibleKeyFrames(id);
+        if ((int)kf.size() >= N) kf.resize((size_t)(N < 0 ? 0 : N));
+        return kf;
+    }
+    std::vector<int32_t> GetCovisiblesByWeight(int id, int w) {
+        std::vector<int32_t> ws, kf = GetVectorCovisibleKeyFrames(id, &ws);
+        if (kf.empty()) return kf;
+        const auto it = std::upper_bound(ws.begin(), ws.end(), w, [](int a, int b) { return a > b; });
+        if (it == ws.end() && ws.back() < w) return {};
+        kf.resize((size_t)(it - ws.begin()));
+        return kf;
+    }
+    orbx_covis_view View() {
+        orbx_covis_view v{};
+        check(orbx_covis_view_device(h_, &v));
+        return v;
+    }
+    orbx_covis* handle() { return h_; }
+
+private:
+    orbx_covis* h_ = nullptr;
+    int maxConn_;
+};
+
 // Optimizer (include/Optimizer.h): the g2o call on the per-frame path, the one of
 // LoopClosing::ComputeSim3 and the one of LocalMapping::Run.
 // PoseOptimization(Frame*) (src/Optimizer.cc:299-502) on the Frame's arrays: mvKeysUn,
@@ -329,6 +399,16 @@ public:
         if (nCorrespondences) *nCorrespondences = counts[1];
         if (nBad) *nBad = counts[2];
         return counts[0];
+    }
+
+    // LocalBundleAdjustment's covisibility walk and edge walk (src/Optimizer.cc:526-583, 656-760)
+    // for the current keyframes a.cur_kf on the graph, into the device tables of
+    // orbx_local_ba_batch (see orbx_local_ba_assemble_device), and the way back (cc:828-853).
+    static void AssembleLocalBundleAdjustment(Covisibility& graph, const orbx_local_ba_assembly& a, void* stream = nullptr) {
+        check(orbx_local_ba_assemble_device(graph.handle(), &a, stream));
+    }
+    static void ApplyLocalBundleAdjustment(Covisibility& graph, const orbx_local_ba_apply& a, void* stream = nullptr) {
+        check(orbx_local_ba_apply_device(graph.handle(), &a, stream));
     }
 
     // LocalBundleAdjustment(pKF, pbStopFlag, pMap) (src/Optimizer.cc:586-853) from the assembled

@@ -7,6 +7,7 @@ include/orbx.h (liborbx.so).  This package is the host-side mirror of the
 reference's ORBextractor / ORBmatcher interface.
 """
 from ._lib import KEYPOINT_DTYPE, OrbxError, lib  # noqa: F401
+from .covisibility import CovisibilityGraph  # noqa: F401
 from .database import KeyFrameDatabase  # noqa: F401
 from .extractor import ORBextractor  # noqa: F401
 from .initializer import Initializer  # noqa: F401
@@ -16,4 +17,4 @@ from .optimizer import essential_graph_edges, essential_graph_envelope  # noqa: 
 from .pnp import PnPsolver  # noqa: F401
 from .sim3 import Sim3Solver  # noqa: F401
 
-__all__ = ["ORBextractor", "EssentialGraphOptimizer", "GlobalBundleAdjuster", "Initializer", "KeyFrameDatabase", "LocalBundleAdjuster", "PnPsolver", "PoseOptimizer", "Sim3Optimizer", "Sim3Solver", "Triangulator", "KEYPOINT_DTYPE", "OrbxError", "lib"]
+__all__ = ["ORBextractor", "CovisibilityGraph", "EssentialGraphOptimizer", "GlobalBundleAdjuster", "Initializer", "KeyFrameDatabase", "LocalBundleAdjuster", "PnPsolver", "PoseOptimizer", "Sim3Optimizer", "Sim3Solver", "Triangulator", "KEYPOINT_DTYPE", "OrbxError", "lib"]

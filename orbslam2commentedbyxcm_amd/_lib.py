@@ -65,6 +65,10 @@ EXPORTED = [
     "orbx_optimize_essential_graph_batch_device", "orbx_optimize_essential_graph", "orbx_essential_graph_envelope",
     "orbx_initializer_create", "orbx_initializer_destroy", "orbx_initializer_initialize_device",
     "orbx_initializer_initialize", "orbx_initializer_sets",
+    "orbx_covis_create", "orbx_covis_destroy", "orbx_covis_stream", "orbx_covis_refresh_observations_device",
+    "orbx_covis_update_connections_device", "orbx_covis_erase_keyframe_device", "orbx_covis_view_device",
+    "orbx_covis_best_covisibles_device", "orbx_covis_covisibles_by_weight_device", "orbx_covis_ordered",
+    "orbx_covis_read", "orbx_covis_refresh_observations", "orbx_local_ba_assemble_device", "orbx_local_ba_apply_device",
 ]
 
 ORBX_DEPTH_U16 = 0
@@ -280,6 +284,38 @@ class InitializerResult(C.Structure):
 ORBX_INIT_MAX_ITERATIONS = 4096
 ORBX_INIT_STATUS_BAD_SET = 1
 ORBX_INIT_STATUS_TOO_FEW = 2
+
+
+ORBX_COVIS_MAX_CONN = 8192
+ORBX_COVIS_LDS_KEYFRAMES = 8192
+ORBX_COVIS_STATUS_CAPACITY = 1
+ORBX_COVIS_STATUS_BAD_KEYFRAME = 2
+ORBX_COVIS_STATUS_DUPLICATE = 4
+
+
+class CovisView(C.Structure):
+    """orbx_covis_view."""
+    _fields_ = [(k, C.c_int) for k in ("max_keyframes", "cap", "max_mappoints", "max_conn", "n_keyframes",
+                                       "n_mappoints")] + \
+               [(k, C.c_void_p) for k in ("obs_off", "obs_kf", "obs_idx", "mp", "row_kf", "row_w", "row_n",
+                                          "ordered_kf", "ordered_w", "ordered_n", "parent", "first", "status")]
+
+
+class LocalBaAssembly(C.Structure):
+    """orbx_local_ba_assembly."""
+    _fields_ = [("batch", C.c_int), ("cur_kf", C.POINTER(C.c_int32)), ("kf_pose", C.c_void_p), ("mp_pos", C.c_void_p),
+                ("max_kf_rows", C.c_int), ("max_pt_rows", C.c_int), ("max_obs", C.c_int)] + \
+               [(k, C.c_void_p) for k in ("kf_off", "kf_Tcw", "kf_fixed", "kf_slot", "kf_id", "pt_off", "pt_pos",
+                                          "pt_id", "obs_off", "obs_kf", "obs_kp", "counts", "status")]
+
+
+class LocalBaApply(C.Structure):
+    """orbx_local_ba_apply."""
+    _fields_ = [("batch", C.c_int), ("max_kf_rows", C.c_int), ("max_pt_rows", C.c_int)] + \
+               [(k, C.c_void_p) for k in ("kf_off", "kf_id", "kf_fixed", "kf_Tcw_opt", "pt_off", "pt_id", "pt_pos_opt",
+                                          "obs_off", "obs_kf", "obs_kp", "erase")] + \
+               [("n_keyframes", C.c_int), ("n_mappoints", C.c_int), ("cap", C.c_int), ("kf_pose", C.c_void_p),
+                ("mp_pos", C.c_void_p), ("kf_mp", C.c_void_p)]
 
 
 # ---- handle lifetime (DESIGN.md §1 "Teardown") ------------------------------------
@@ -510,6 +546,22 @@ def lib() -> C.CDLL:
     L.orbx_initializer_initialize_device.argtypes = [vp, C.POINTER(InitializerBatch), C.POINTER(InitializerResult), vp]
     L.orbx_initializer_initialize.argtypes = [vp, C.POINTER(InitializerBatch), C.POINTER(InitializerResult)]
     L.orbx_initializer_sets.argtypes = [i32p, C.c_int, C.c_int]
+    L.orbx_covis_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.orbx_covis_destroy.argtypes = [vp]
+    L.orbx_covis_destroy.restype = None
+    L.orbx_covis_stream.argtypes = [vp]
+    L.orbx_covis_stream.restype = vp
+    L.orbx_covis_refresh_observations_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp]
+    L.orbx_covis_refresh_observations.argtypes = [vp, C.c_int, i32p, i32p, u8p, C.c_int, u8p]
+    L.orbx_covis_update_connections_device.argtypes = [vp, i32p, C.c_int, vp]
+    L.orbx_covis_erase_keyframe_device.argtypes = [vp, C.c_int, vp]
+    L.orbx_covis_view_device.argtypes = [vp, C.POINTER(CovisView)]
+    L.orbx_covis_best_covisibles_device.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.orbx_covis_covisibles_by_weight_device.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.orbx_local_ba_assemble_device.argtypes = [vp, C.POINTER(LocalBaAssembly), vp]
+    L.orbx_local_ba_apply_device.argtypes = [vp, C.POINTER(LocalBaApply), vp]
+    L.orbx_covis_read.argtypes = [vp, vp, vp, C.c_size_t]
+    L.orbx_covis_ordered.argtypes = [vp, C.c_int, i32p, i32p, C.c_int, ip]
     L.orbx_version.restype = C.c_char_p
     L.orbx_device_count.argtypes = [ip]
     L.orbx_last_error.restype = C.c_char_p

@@ -288,7 +288,8 @@ class LocalBundleAdjuster(PoseOptimizer):
     """Optimizer::LocalBundleAdjustment (src/Optimizer.cc:586-853) on the GPU
     (csrc/orbx_localba.hip): LocalBundleAdjustment for one local map on host arrays and
     local_ba_batch_device for B local maps in HBM.  The covisibility walk that chooses the
-    keyframes and points stays with the caller; the stop flag is not supported.  The handle,
+    keyframes and points is the caller's, or assemble_batch_device's on a CovisibilityGraph
+    (csrc/orbx_covis.hip), with apply_batch_device for the way back; the stop flag is not supported.  The handle,
     close() and last_call_us() are PoseOptimizer's."""
 
     def LocalBundleAdjustment(self, kf_Tcw, kf_fixed, kf_slot, pt_pos, obs_off, obs_kf, obs_kp, keys_un, u_right,
@@ -362,6 +363,82 @@ class LocalBundleAdjuster(PoseOptimizer):
         q.n_erase, q.trace, q.status = ptr(d_n_erase), ptr(d_trace), ptr(d_status)
         s = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
         L.check(L.lib().orbx_local_bundle_adjustment_batch_device(self._h, C.byref(q), s))
+
+    ASSEMBLY_TABLES = (("kf_off", "B1", "int32"), ("kf_Tcw", "K12", "float32"), ("kf_fixed", "K", "uint8"),
+                       ("kf_slot", "K", "int32"), ("kf_id", "K", "int32"), ("pt_off", "B1", "int32"),
+                       ("pt_pos", "P3", "float32"), ("pt_id", "P", "int32"), ("obs_off", "P1", "int32"),
+                       ("obs_kf", "O", "int32"), ("obs_kp", "O", "int32"), ("counts", "B3", "int32"),
+                       ("status", "B", "int32"))
+
+    def assemble_batch_device(self, graph, cur_kf, d_kf_pose, d_mp_pos, max_kf_rows: int, max_pt_rows: int,
+                              max_obs: int, tables: dict | None = None, stream=None) -> dict:
+        """orbx_local_ba_assemble_device: the covisibility walk of Optimizer.cc:526-583 and the
+        edge walk of cc:656-760 for the current keyframes cur_kf (host ints) on `graph` (a
+        CovisibilityGraph, refreshed), into the tables of local_ba_batch_device plus kf_id, pt_id,
+        counts (B, 3) and status (B,).  d_kf_pose (K, 12) / d_mp_pos (n, 3) f32 device tensors by
+        id; the capacities are for the whole batch.  Returns the tables (device tensors; those
+        passed in `tables` are reused).  Nothing is read back.  Asynchronous."""
+        import torch
+        cur = np.ascontiguousarray(np.atleast_1d(cur_kf), dtype=np.int32)
+        B, K, P, O = len(cur), int(max_kf_rows), int(max_pt_rows), int(max_obs)
+        shapes = {"B": (B,), "B1": (B + 1,), "B3": (B, 3), "K": (K,), "K12": (K, 12), "P": (P,), "P1": (P + 1,),
+                  "P3": (P, 3), "O": (O,)}
+        t = dict(tables or {})
+        for name, shape, dtype in self.ASSEMBLY_TABLES:
+            if name not in t:
+                t[name] = torch.zeros(shapes[shape], dtype=getattr(torch, dtype), device=d_kf_pose.device)
+            elif tuple(t[name].shape) != shapes[shape]:
+                raise ValueError(f"{name}: shape {tuple(t[name].shape)}, expected {shapes[shape]}")
+        a = L.LocalBaAssembly()
+        a.batch, a.cur_kf = B, L.i32ptr(cur if B else np.zeros(1, np.int32))
+        a.kf_pose, a.mp_pos = d_kf_pose.data_ptr(), d_mp_pos.data_ptr()
+        a.max_kf_rows, a.max_pt_rows, a.max_obs = K, P, O
+        for name, _, _ in self.ASSEMBLY_TABLES:
+            setattr(a, name, t[name].data_ptr())
+        s = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        L.check(L.lib().orbx_local_ba_assemble_device(graph._h, C.byref(a), s))
+        return t
+
+    def local_ba_assembled_device(self, tables: dict, d_kps, d_u_right, inv_level_sigma2, fx, fy, cx, cy, bf,
+                                  out: dict | None = None, max_free_kf: int = 0, stream=None) -> dict:
+        """local_ba_batch_device on the tables of assemble_batch_device (the capacities stand in
+        for the sizes).  Returns kf_Tcw_opt, pt_pos_opt, erase, level1, n_erase, trace, status
+        (device tensors; those passed in `out` are reused)."""
+        import torch
+        B = int(tables["kf_off"].shape[0]) - 1
+        dev = tables["kf_off"].device
+        o = dict(out or {})
+        for name, like, dtype in (("kf_Tcw_opt", tables["kf_Tcw"].shape, torch.float32),
+                                  ("pt_pos_opt", tables["pt_pos"].shape, torch.float32),
+                                  ("erase", tables["obs_kf"].shape, torch.uint8),
+                                  ("level1", tables["obs_kf"].shape, torch.uint8), ("n_erase", (B,), torch.int32),
+                                  ("trace", (B, 2, 2), torch.int32), ("status", (B,), torch.int32)):
+            if name not in o:
+                o[name] = torch.zeros(tuple(like), dtype=dtype, device=dev)
+        self.local_ba_batch_device(tables["kf_off"], tables["kf_Tcw"], tables["kf_fixed"], tables["kf_slot"],
+                                   tables["pt_off"], tables["pt_pos"], tables["obs_off"], tables["obs_kf"],
+                                   tables["obs_kp"], d_kps, d_u_right, inv_level_sigma2, fx, fy, cx, cy, bf,
+                                   o["kf_Tcw_opt"], o["pt_pos_opt"], o["erase"], o["n_erase"], o["status"],
+                                   d_level1=o["level1"], d_trace=o["trace"], max_free_kf=max_free_kf, stream=stream)
+        return o
+
+    def apply_batch_device(self, graph, tables: dict, d_kf_Tcw_opt, d_pt_pos_opt, d_erase, d_kf_pose, d_mp_pos,
+                           d_kf_mp=None, stream=None) -> None:
+        """orbx_local_ba_apply_device, the index part of Optimizer.cc:828-853: the optimised
+        poses of the keyframes that are not fixed to d_kf_pose, the positions to d_mp_pos, and
+        d_kf_mp[keyframe][keypoint] = -1 for every erase[o].  Asynchronous."""
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        a = L.LocalBaApply()
+        a.batch = int(tables["kf_off"].shape[0]) - 1
+        a.max_kf_rows, a.max_pt_rows = int(tables["kf_id"].shape[0]), int(tables["pt_id"].shape[0])
+        for name in ("kf_off", "kf_id", "kf_fixed", "pt_off", "pt_id", "obs_off", "obs_kf", "obs_kp"):
+            setattr(a, name, tables[name].data_ptr())
+        a.kf_Tcw_opt, a.pt_pos_opt, a.erase = ptr(d_kf_Tcw_opt), ptr(d_pt_pos_opt), ptr(d_erase)
+        a.n_keyframes, a.n_mappoints = int(d_kf_pose.shape[0]), int(d_mp_pos.shape[0])
+        a.cap = 0 if d_kf_mp is None else int(d_kf_mp.shape[1])
+        a.kf_pose, a.mp_pos, a.kf_mp = ptr(d_kf_pose), ptr(d_mp_pos), ptr(d_kf_mp)
+        s = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        L.check(L.lib().orbx_local_ba_apply_device(graph._h, C.byref(a), s))
 
 
 def global_ba_envelope(kf_fixed, obs_off, obs_kf) -> int:
