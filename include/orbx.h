@@ -1834,6 +1834,98 @@ typedef struct {
 } orbx_local_ba_apply;
 int orbx_local_ba_apply_device(orbx_covis* g, const orbx_local_ba_apply* a, void* stream);
 
+/* ---- Tracking::UpdateLocalMap and TrackLocalMap's tally on the device ----
+ * orbx_update_local_map_device runs Tracking::UpdateLocalKeyFrames and UpdateLocalPoints
+ * (Tracking.cc:1342-1500) for B frames on the covisibility graph `g`, whose observations are
+ * those of the last refresh.  The keyframe id stands in for KeyFrame* wherever the reference
+ * iterates a map or set of pointers.  For frame b, literally:
+ *   votes (cc:1393-1408): for each index i < min(n[b], cap) of frame_mp[b], an id that is
+ *   negative or outside [0, n_mappoints) counts as NULL, a bad MapPoint is written back as -1
+ *   (cc:1405), every other entry adds one vote to each of its observers (a MapPoint at two
+ *   indices votes twice);
+ *   an empty counter (cc:1411) sets ORBX_LOCAL_MAP_STATUS_EMPTY and leaves local_kf[b],
+ *   local_kf_n[b] (in/out; the count is clamped into [0, max_local_kf], ids outside the graph's
+ *   keyframes contribute no points) and ref_kf[b] as they are on entry; UpdateLocalPoints still
+ *   runs over that list;
+ *   strategy 1 (cc:1423-1442): the voted keyframes in ascending id; pKFmax is the lowest id among
+ *   the maxima.  The observation CSR holds no keyframe that was bad at the refresh, so the
+ *   isBad() skip cannot fire through it; the test is kept because kf_bad is read when the call
+ *   runs and may have changed since;
+ *   strategy 2 (cc:1445-1493) over the strategy-1 entries only, in order, stopping once the list
+ *   holds more than 80: the first of the entry's best 10 ordered neighbours that is neither bad
+ *   nor local, then its first child in ascending id that is neither, then its parent, which is
+ *   not tested for badness -- a parent that was not yet local is appended and ends the whole
+ *   walk (the reference's break leaves the outer loop).  The children of k are the keyframes c
+ *   that are not bad and have parent[c] == k; `parent` is the graph's own array unless the
+ *   caller passes one (after culling or a loop closure the caller owns the spanning tree);
+ *   ref_kf[b] = pKFmax when there is one;
+ *   UpdateLocalPoints (cc:1354-1380): the local keyframes in list order, each row of the graph's
+ *   cleaned table in index order (whether or not the keyframe is bad now), the first appearance
+ *   of every MapPoint that is not bad.
+ * Everything is written on the device and nothing is read back: local_kf [B][max_local_kf] with
+ * local_kf_n [B], ref_kf [B], local_off [B + 1] (compact over the batch), local_ids [max_total],
+ * counts [B][2] = {local keyframes, local points} and status [B].  A frame whose list exceeds
+ * max_local_kf, whose points exceed max_local_points, or whose points do not fit what the
+ * frames before it left of max_total gets ORBX_LOCAL_MAP_STATUS_CAPACITY, local_kf_n = 0, an
+ * empty range, zero counts, and ref_kf and frame_mp as if untouched (its row of local_kf is
+ * unspecified); every other frame is laid out as if that frame were not there.  This is a
+ * deviation outside the reference.  Entries of local_kf behind local_kf_n are unspecified.
+ * ORBX_ERR_ARG, decided before any device call: a null required pointer, a negative size, cap
+ * different from the graph's, a call before any refresh.  Every pointer is a device pointer.
+ * Asynchronous on `stream` (or the graph's). */
+#define ORBX_LOCAL_MAP_STATUS_CAPACITY 1
+#define ORBX_LOCAL_MAP_STATUS_EMPTY 2
+typedef struct {
+    int batch;
+    int cap;                   /* row length of frame_mp: the graph's cap */
+    int32_t* frame_mp;         /* [B][cap] mCurrentFrame.mvpMapPoints as ids, in/out */
+    const int32_t* n;          /* [B] mCurrentFrame.N */
+    const int32_t* parent;     /* [max_keyframes] mpParent, -1 = NULL; NULL: the graph's */
+    int max_local_kf, max_local_points, max_total;
+    int32_t* local_kf;         /* [B][max_local_kf] mvpLocalKeyFrames, in/out */
+    int32_t* local_kf_n;       /* [B] in/out */
+    int32_t* ref_kf;           /* [B] mpReferenceKF, in/out */
+    int32_t* local_off;        /* [B + 1] out */
+    int32_t* local_ids;        /* [max_total] mvpLocalMapPoints, frame after frame, out */
+    int32_t* counts;           /* [B][2] out */
+    int32_t* status;           /* [B] out */
+} orbx_local_map_update;
+int orbx_update_local_map_device(orbx_covis* g, const orbx_local_map_update* u, void* stream);
+/* The host form: every array of `u` on the host, staged through the graph's own buffer on the
+ * graph's stream; synchronises. */
+int orbx_update_local_map(orbx_covis* g, const orbx_local_map_update* u);
+
+/* orbx_search_local_points_device with local_off as a device array, taken as written by
+ * orbx_update_local_map_device: lm->local_off is ignored, the scratch is sized by max_total and
+ * the launch by max_local_points, and each frame's range is clamped into both bounds, so that a
+ * wrong offset is never read or written past them.  Nothing is read back. */
+int orbx_search_local_points_offsets_device(orbx_matcher* m, const orbx_mappoints_device* mps,
+                                            const orbx_local_map_batch* lm, const int32_t* d_local_off,
+                                            int max_local_points, int max_total, void* stream);
+
+/* TrackLocalMap's tally after the second PoseOptimization (Tracking.cc:1047-1081) for B frames:
+ * matches_inliers[b] counts the entries i < min(n[b], cap) of frame_mp[b] that are not NULL (an id
+ * outside [0, n_mappoints) counts as NULL), not outliers and, unless only_tracking, have
+ * observations > 0; each entry that is not an outlier adds one to mp_found[id] (IncreaseFound(),
+ * an integer atomicAdd whose sum does not depend on order; NULL: skipped); with `stereo` an
+ * outlier's entry becomes -1; ok[b] = 0 when matches_inliers[b] < 30, or < 50 with
+ * recently_relocalised[b] (NULL: no frame), else 1.  IncreaseVisible is done by the search.
+ * Device pointers; runs on the graph's device, asynchronous on `stream` (or the graph's). */
+typedef struct {
+    int batch, cap;
+    int32_t* frame_mp;                    /* [B][cap] in/out */
+    const int32_t* n;                     /* [B] */
+    const uint8_t* outlier;               /* [B][cap] mvbOutlier */
+    int n_mappoints;
+    const int32_t* observations;          /* [n_mappoints] Observations() */
+    int only_tracking, stereo;
+    const uint8_t* recently_relocalised;  /* [B] mnId < mnLastRelocFrameId + mMaxFrames, or NULL */
+    int32_t* mp_found;                    /* [n_mappoints] mnFound, in/out, or NULL */
+    int32_t* matches_inliers;             /* [B] out */
+    uint8_t* ok;                          /* [B] out */
+} orbx_track_local_map_tally;
+int orbx_track_local_map_tally_device(orbx_covis* g, const orbx_track_local_map_tally* t, void* stream);
+
 /* Alternative kernel forms and diagnostics switches, process-wide (tests and A/B tools;
  * the product reads no environment).  Names: "pz_seg" (pyramid levels per launch, 0 = one
  * launch), "pz_byte" (byte-read k_pyramid), "desc_tiles" (tile-major describe),

@@ -307,6 +307,80 @@ private:
     int maxConn_;
 };
 
+// Tracking's local map (src/Tracking.cc:1342-1500) and TrackLocalMap's tally (cc:1047-1081) on a
+// Covisibility graph: frames are rows of a [frames][cap] MapPoint id table (-1 = NULL).
+class Tracking {
+public:
+    explicit Tracking(Covisibility& graph) : g_(graph) {}
+
+    // mvpLocalKeyFrames / mpReferenceKF / mvpLocalMapPoints of a batch of frames; the first three
+    // are in/out and persist from call to call (an empty counter keeps them)
+    struct LocalMaps {
+        int maxLocalKeyFrames = 0;
+        std::vector<int32_t> localKeyFrames;   // [frames][maxLocalKeyFrames]
+        std::vector<int32_t> nLocalKeyFrames;  // [frames]
+        std::vector<int32_t> referenceKF;      // [frames]
+        std::vector<int32_t> localOff;         // [frames + 1]
+        std::vector<int32_t> localMapPoints;   // frame b: [localOff[b], localOff[b + 1])
+        std::vector<int32_t> counts, status;   // [frames][2], [frames] ORBX_LOCAL_MAP_STATUS_*
+    };
+
+    // UpdateLocalMap() on device arrays: everything is written there, nothing is read back
+    void UpdateLocalMap(const orbx_local_map_update& u, void* stream = nullptr) {
+        check(orbx_update_local_map_device(g_.handle(), &u, stream));
+    }
+    // ... or on host vectors: mvpMapPoints [frames][cap] (bad MapPoints become -1), N [frames];
+    // parent empty: the graph's own mpParent.  lm is (re)initialised when its shape differs.
+    void UpdateLocalMap(std::vector<int32_t>& mvpMapPoints, const std::vector<int32_t>& N, int cap, LocalMaps& lm,
+                        int maxLocalKeyFrames, int maxLocalPoints, int maxTotal,
+                        const std::vector<int32_t>& parent = std::vector<int32_t>()) {
+        const size_t B = N.size();
+        if (lm.maxLocalKeyFrames != maxLocalKeyFrames || lm.nLocalKeyFrames.size() != B) {
+            lm.maxLocalKeyFrames = maxLocalKeyFrames;
+            lm.localKeyFrames.assign(B * (size_t)maxLocalKeyFrames, -1);
+            lm.nLocalKeyFrames.assign(B, 0);
+            lm.referenceKF.assign(B, -1);
+        }
+        lm.localOff.assign(B + 1, 0);
+        lm.localMapPoints.assign((size_t)maxTotal, -1);
+        lm.counts.assign(2 * B, 0);
+        lm.status.assign(B, 0);
+        orbx_local_map_update u{};
+        u.batch = (int)B;
+        u.cap = cap;
+        u.frame_mp = mvpMapPoints.data();
+        u.n = N.data();
+        u.parent = parent.empty() ? nullptr : parent.data();
+        u.max_local_kf = maxLocalKeyFrames;
+        u.max_local_points = maxLocalPoints;
+        u.max_total = maxTotal;
+        u.local_kf = lm.localKeyFrames.data();
+        u.local_kf_n = lm.nLocalKeyFrames.data();
+        u.ref_kf = lm.referenceKF.data();
+        u.local_off = lm.localOff.data();
+        u.local_ids = lm.localMapPoints.data();
+        u.counts = lm.counts.data();
+        u.status = lm.status.data();
+        check(orbx_update_local_map(g_.handle(), &u));
+        lm.localMapPoints.resize((size_t)lm.localOff[B]);
+    }
+
+    // SearchLocalPoints() on the lists that UpdateLocalMap wrote on the device
+    static void SearchLocalPoints(ORBmatcher& matcher, const orbx_mappoints_device& mps, const orbx_local_map_batch& lm,
+                                  const int32_t* d_local_off, int maxLocalPoints, int maxTotal, void* stream = nullptr) {
+        check(orbx_search_local_points_offsets_device(matcher.handle(), &mps, &lm, d_local_off, maxLocalPoints, maxTotal,
+                                                      stream));
+    }
+
+    // mnMatchesInliers and TrackLocalMap's verdict after the second PoseOptimization
+    void TrackLocalMapTally(const orbx_track_local_map_tally& t, void* stream = nullptr) {
+        check(orbx_track_local_map_tally_device(g_.handle(), &t, stream));
+    }
+
+private:
+    Covisibility& g_;
+};
+
 // Optimizer (include/Optimizer.h): the g2o call on the per-frame path, the one of
 // LoopClosing::ComputeSim3 and the one of LocalMapping::Run.
 // PoseOptimization(Frame*) (src/Optimizer.cc:299-502) on the Frame's arrays: mvKeysUn,

@@ -12,9 +12,11 @@ from .database import KeyFrameDatabase  # noqa: F401
 from .extractor import ORBextractor  # noqa: F401
 from .initializer import Initializer  # noqa: F401
 from .mapping import Triangulator  # noqa: F401
+from .matcher import ORBmatcher  # noqa: F401
 from .optimizer import EssentialGraphOptimizer, GlobalBundleAdjuster, LocalBundleAdjuster, PoseOptimizer, Sim3Optimizer  # noqa: F401
 from .optimizer import essential_graph_edges, essential_graph_envelope  # noqa: F401
 from .pnp import PnPsolver  # noqa: F401
 from .sim3 import Sim3Solver  # noqa: F401
+from .tracking import LocalMapTracker  # noqa: F401
 
-__all__ = ["ORBextractor", "CovisibilityGraph", "EssentialGraphOptimizer", "GlobalBundleAdjuster", "Initializer", "KeyFrameDatabase", "LocalBundleAdjuster", "PnPsolver", "PoseOptimizer", "Sim3Optimizer", "Sim3Solver", "Triangulator", "KEYPOINT_DTYPE", "OrbxError", "lib"]
+__all__ = ["ORBextractor", "CovisibilityGraph", "EssentialGraphOptimizer", "GlobalBundleAdjuster", "Initializer", "KeyFrameDatabase", "LocalBundleAdjuster", "LocalMapTracker", "ORBmatcher", "PnPsolver", "PoseOptimizer", "Sim3Optimizer", "Sim3Solver", "Triangulator", "KEYPOINT_DTYPE", "OrbxError", "lib"]

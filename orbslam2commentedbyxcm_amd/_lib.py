@@ -69,6 +69,8 @@ EXPORTED = [
     "orbx_covis_update_connections_device", "orbx_covis_erase_keyframe_device", "orbx_covis_view_device",
     "orbx_covis_best_covisibles_device", "orbx_covis_covisibles_by_weight_device", "orbx_covis_ordered",
     "orbx_covis_read", "orbx_covis_refresh_observations", "orbx_local_ba_assemble_device", "orbx_local_ba_apply_device",
+    "orbx_update_local_map_device", "orbx_update_local_map", "orbx_search_local_points_offsets_device",
+    "orbx_track_local_map_tally_device",
 ]
 
 ORBX_DEPTH_U16 = 0
@@ -318,6 +320,25 @@ class LocalBaApply(C.Structure):
                 ("mp_pos", C.c_void_p), ("kf_mp", C.c_void_p)]
 
 
+ORBX_LOCAL_MAP_STATUS_CAPACITY = 1
+ORBX_LOCAL_MAP_STATUS_EMPTY = 2
+
+
+class LocalMapUpdate(C.Structure):
+    """orbx_local_map_update."""
+    _fields_ = [("batch", C.c_int), ("cap", C.c_int), ("frame_mp", C.c_void_p), ("n", C.c_void_p), ("parent", C.c_void_p),
+                ("max_local_kf", C.c_int), ("max_local_points", C.c_int), ("max_total", C.c_int)] + \
+               [(k, C.c_void_p) for k in ("local_kf", "local_kf_n", "ref_kf", "local_off", "local_ids", "counts", "status")]
+
+
+class TrackLocalMapTally(C.Structure):
+    """orbx_track_local_map_tally."""
+    _fields_ = [("batch", C.c_int), ("cap", C.c_int), ("frame_mp", C.c_void_p), ("n", C.c_void_p), ("outlier", C.c_void_p),
+                ("n_mappoints", C.c_int), ("observations", C.c_void_p), ("only_tracking", C.c_int), ("stereo", C.c_int),
+                ("recently_relocalised", C.c_void_p), ("mp_found", C.c_void_p), ("matches_inliers", C.c_void_p),
+                ("ok", C.c_void_p)]
+
+
 # ---- handle lifetime (DESIGN.md §1 "Teardown") ------------------------------------
 # Every object that owns liborbx handles or HIP streams registers here.  At interpreter
 # exit the atexit hook synchronises the devices and closes them newest first -- while the
@@ -561,6 +582,11 @@ def lib() -> C.CDLL:
     L.orbx_local_ba_assemble_device.argtypes = [vp, C.POINTER(LocalBaAssembly), vp]
     L.orbx_local_ba_apply_device.argtypes = [vp, C.POINTER(LocalBaApply), vp]
     L.orbx_covis_read.argtypes = [vp, vp, vp, C.c_size_t]
+    L.orbx_update_local_map_device.argtypes = [vp, C.POINTER(LocalMapUpdate), vp]
+    L.orbx_update_local_map.argtypes = [vp, C.POINTER(LocalMapUpdate)]
+    L.orbx_search_local_points_offsets_device.argtypes = [vp, C.POINTER(MapPointsDevice), C.POINTER(LocalMapBatch), vp,
+                                                          C.c_int, C.c_int, vp]
+    L.orbx_track_local_map_tally_device.argtypes = [vp, C.POINTER(TrackLocalMapTally), vp]
     L.orbx_covis_ordered.argtypes = [vp, C.c_int, i32p, i32p, C.c_int, ip]
     L.orbx_version.restype = C.c_char_p
     L.orbx_device_count.argtypes = [ip]

@@ -40,72 +40,21 @@
 
 #include "orbx.h"
 #include "orbx_block_sort.h"
+#include "orbx_covis.h"
 #include "orbx_host.h"
 
 namespace orbx {
 namespace {
 
-constexpr int kCvThreads = kSortThreads;
-constexpr int kCvWaves = kCvThreads / 64;
 constexpr int kCvTh = 15;          // KeyFrame.cc:362
 constexpr int kCvGroups = 128;     // workgroups of a launch that takes a global dense row each
 constexpr int kCvMaxKeyframes = 1 << 20;
-
-struct CovisDev {
-    int K, cap, n, max_conn, dense_lds;  // dense_lds: the dense row lives in LDS
-    int nk, nm;                          // keyframes / MapPoints of the last refresh
-    const int32_t* kf_n;
-    const uint8_t* kf_bad;
-    const uint8_t* mp_bad;
-    int32_t* clean;    // [K][cap] mvpMapPoints without NULL, out-of-range ids and later copies
-    int32_t* obs_off;  // [n + 1]
-    int32_t* obs_cnt;  // [n] counts, then cursors
-    int32_t* obs_kf;   // [K * cap]
-    int32_t* obs_idx;  // [K * cap]
-    int32_t* tmp_kf;   // [K * cap] observers in arrival order
-    int32_t *row_kf, *row_w, *row_n;  // mConnectedKeyFrameWeights, ascending id
-    int32_t *ord_kf, *ord_w, *ord_n;  // mvpOrderedConnectedKeyFrames / mvOrderedWeights
-    int32_t* parent;                  // mpParent, -1 = NULL
-    uint8_t* first;                   // mbFirstConnection
-    int32_t* status;
-    int32_t* kmax;   // per fresh keyframe: pKFmax when no entry reached th, else -1
-    uint8_t* fresh;  // rewritten by the running batch
-    int32_t* ws;     // [kCvGroups][K] dense rows when they do not fit LDS
-};
 
 struct CvScratch {
     int w[kCvWaves];
     int m, n15;
     unsigned long long best;
 };
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// Words that atomics update in L2 are read and reset past the vector L1, which an atomic leaves stale.
-__device__ __forceinline__ int cv_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void cv_st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// exclusive prefix of v over the workgroup's threads in thread order; every thread gets the total
-__device__ int cv_block_scan(int v, int* s_w, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    int before = 0, tot = 0;
-    for (int w = 0; w < kCvWaves; w++) {
-        const int c = s_w[w];
-        if (w < wave) before += c;
-        tot += c;
-    }
-    __syncthreads();
-    total = tot;
-    return before + inc - v;
-}
 
 // Entries, entries >= th and the maximum (the lowest id among equal weights: the strict > in
 // ascending id order, cc:370) of a dense row; then, unless it is empty or exceeds max_conn,
@@ -442,14 +391,6 @@ __global__ void k_covis_by_weight(CovisDev D, int w, int32_t* out, int32_t* out_
 constexpr int kAsmGroups = 64;
 constexpr int kAsmNone = INT_MAX;
 
-struct AsmWs {
-    int32_t* pmark;  // [kAsmGroups][n]
-    int32_t* kmark;  // [kAsmGroups][K]
-    int32_t* loc;    // [kAsmGroups][max_conn + 1] lLocalKeyFrames
-    int32_t* raw;    // [B][3] what each problem needs
-    int32_t* base;   // [B][3] where it goes
-};
-
 __device__ void cv_assemble(const CovisDev& D, const orbx_local_ba_assembly& A, const AsmWs& W, int b, int cur, bool write, int* s_w) {
     const int tid = threadIdx.x;
     int* pmark = W.pmark + (size_t)blockIdx.x * D.n;
@@ -656,37 +597,18 @@ __global__ void k_covis_apply_pt(orbx_local_ba_apply A) {
 }  // namespace
 }  // namespace orbx
 
-struct orbx_covis {
-    orbx::CovisDev D{};
-    int device = 0;
-    hipStream_t stream = nullptr, last = nullptr;
-    std::vector<void*> allocs;
-    int32_t* ids = nullptr;  // [K] a batch's ids
-    std::vector<int32_t> h_ids;
-    size_t lds = 0;
-    bool refreshed = false;
-    orbx::AsmWs asm_ws{};  // allocated by the first assembly
-    orbx::DeviceBuffer asm_batch;
-    orbx::DeviceBuffer host_map;  // the host form's copy of the map
-};
-
 namespace {
 
 using namespace orbx;
-
-int enter(orbx_covis* h, void* stream, hipStream_t* s) {
-    HIP_TRY(hipSetDevice(h->device));
-    *s = stream ? (hipStream_t)stream : h->stream;
-    if (h->last && h->last != *s) HIP_TRY(hipStreamSynchronize(h->last));
-    h->last = *s;
-    return ORBX_OK;
-}
 
 void free_covis(orbx_covis* h) {
     for (void* p : h->allocs)
         if (p) (void)hipFree(p);
     h->asm_batch.release();
     h->host_map.release();
+    h->lm_ws_buf.release();
+    h->lm_batch.release();
+    h->lm_host.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
 }
 
@@ -783,7 +705,7 @@ int orbx_covis_refresh_observations_device(orbx_covis* h, int n_keyframes, const
         return fail(ORBX_ERR_ARG, "more keyframes or MapPoints than the graph was created for");
     if (n_keyframes > 0 && (!kf_mp || !kf_n)) return fail(ORBX_ERR_ARG, "null keyframe table");
     hipStream_t s;
-    int rc = enter(h, stream, &s);
+    int rc = covis_enter(h, stream, &s);
     if (rc) return rc;
     CovisDev& D = h->D;
     D.nk = n_keyframes;
@@ -822,7 +744,7 @@ int orbx_covis_refresh_observations(orbx_covis* h, int n_keyframes, const int32_
         return fail(ORBX_ERR_ARG, "more keyframes or MapPoints than the graph was created for");
     if (n_keyframes > 0 && (!kf_mp || !kf_n)) return fail(ORBX_ERR_ARG, "null keyframe table");
     hipStream_t s;
-    int rc = enter(h, nullptr, &s);
+    int rc = covis_enter(h, nullptr, &s);
     if (rc) return rc;
     // the graph keeps kf_n and the bad flags for the later calls: they live in its own copy
     const size_t nk = (size_t)n_keyframes, table = nk * h->D.cap * 4;
@@ -853,7 +775,7 @@ int orbx_covis_update_connections_device(orbx_covis* h, const int32_t* ids, int 
     if (!h->refreshed) return fail(ORBX_ERR_STATE, "no observations: call orbx_covis_refresh_observations_device first");
     if (Q == 0) return ORBX_OK;
     hipStream_t s;
-    int rc = enter(h, stream, &s);
+    int rc = covis_enter(h, stream, &s);
     if (rc) return rc;
     const CovisDev& D = h->D;
     h->h_ids.swap(sorted);
@@ -877,7 +799,7 @@ int orbx_covis_erase_keyframe_device(orbx_covis* h, int id, void* stream) {
     if (!h || id < 0 || id >= h->D.K) return fail(ORBX_ERR_ARG, "bad argument");
     if (id == 0) return ORBX_OK;  // cc:497
     hipStream_t s;
-    int rc = enter(h, stream, &s);
+    int rc = covis_enter(h, stream, &s);
     if (rc) return rc;
     static thread_local bool attr = false;
     if (!attr) {
@@ -902,7 +824,7 @@ int orbx_covis_view_device(orbx_covis* h, orbx_covis_view* v) {
 int orbx_covis_best_covisibles_device(orbx_covis* h, int N, int32_t* out, int32_t* out_n, void* stream) {
     if (!h || N < 1 || !out || !out_n) return fail(ORBX_ERR_ARG, "bad argument");
     hipStream_t s;
-    int rc = enter(h, stream, &s);
+    int rc = covis_enter(h, stream, &s);
     if (rc) return rc;
     const long long total = (long long)h->D.K * N;
     k_covis_best<<<(int)((total + 255) / 256), 256, 0, s>>>(h->D, N, out, out_n);
@@ -913,7 +835,7 @@ int orbx_covis_best_covisibles_device(orbx_covis* h, int N, int32_t* out, int32_
 int orbx_covis_covisibles_by_weight_device(orbx_covis* h, int w, int32_t* out, int32_t* out_n, void* stream) {
     if (!h || !out_n) return fail(ORBX_ERR_ARG, "bad argument");
     hipStream_t s;
-    int rc = enter(h, stream, &s);
+    int rc = covis_enter(h, stream, &s);
     if (rc) return rc;
     k_covis_by_weight<<<(h->D.K + 255) / 256, 256, 0, s>>>(h->D, w, out, out_n);
     HIP_TRY(hipGetLastError());
@@ -923,7 +845,7 @@ int orbx_covis_covisibles_by_weight_device(orbx_covis* h, int w, int32_t* out, i
 int orbx_covis_read(orbx_covis* h, const void* src, void* dst, size_t bytes) {
     if (!h || (bytes && (!src || !dst))) return fail(ORBX_ERR_ARG, "bad argument");
     hipStream_t s;
-    int rc = enter(h, nullptr, &s);
+    int rc = covis_enter(h, nullptr, &s);
     if (rc) return rc;
     if (bytes) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -933,7 +855,7 @@ int orbx_covis_read(orbx_covis* h, const void* src, void* dst, size_t bytes) {
 int orbx_covis_ordered(orbx_covis* h, int id, int32_t* kf, int32_t* w, int cap, int* n) {
     if (!h || id < 0 || id >= h->D.K || cap < 0 || !n || (cap > 0 && !kf)) return fail(ORBX_ERR_ARG, "bad argument");
     hipStream_t s;
-    int rc = enter(h, nullptr, &s);
+    int rc = covis_enter(h, nullptr, &s);
     if (rc) return rc;
     const CovisDev& D = h->D;
     int32_t cnt = 0;
@@ -961,7 +883,7 @@ int orbx_local_ba_assemble_device(orbx_covis* h, const orbx_local_ba_assembly* a
         if (a->cur_kf[b] < 0 || a->cur_kf[b] >= h->D.K) return fail(ORBX_ERR_ARG, "keyframe id outside the graph");
     if (!h->refreshed) return fail(ORBX_ERR_STATE, "no observations: call orbx_covis_refresh_observations_device first");
     hipStream_t s;
-    int rc = enter(h, stream, &s);
+    int rc = covis_enter(h, stream, &s);
     if (rc) return rc;
     const CovisDev& D = h->D;
     AsmWs& W = h->asm_ws;
@@ -1008,7 +930,7 @@ int orbx_local_ba_apply_device(orbx_covis* h, const orbx_local_ba_apply* a, void
         (a->erase && a->kf_mp && (!a->obs_kf || !a->obs_kp || !a->kf_id)))
         return fail(ORBX_ERR_ARG, "null table");
     hipStream_t s;
-    int rc = enter(h, stream, &s);
+    int rc = covis_enter(h, stream, &s);
     if (rc) return rc;
     if (a->max_kf_rows > 0) {
         k_covis_apply_kf<<<(a->max_kf_rows + 255) / 256, 256, 0, s>>>(*a);

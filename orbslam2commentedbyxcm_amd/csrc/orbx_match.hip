@@ -2103,7 +2103,11 @@ __global__ __launch_bounds__(kLocalThreads) void k_local_build(LocalArgs A, Proj
         }
     }
     __syncthreads();
-    const int lo = A.local_off[b], hi = A.local_off[b + 1];
+    // never past the tables, whatever the offsets hold (orbx.h, orbx_search_local_points_offsets_device)
+    int lo = A.local_off[b], hi = A.local_off[b + 1];
+    lo = lo < 0 ? 0 : (lo > A.max_total ? A.max_total : lo);
+    hi = hi > A.max_total ? A.max_total : hi;
+    hi = hi < lo ? lo : (hi - lo > A.max_points ? lo + A.max_points : hi);
     const float* T = A.Tcw + 12 * (size_t)b;
     float Ow[3];  // mOw = -Rcw^T tcw
     for (int c = 0; c < 3; c++) Ow[c] = -(T[c] * T[3] + T[4 + c] * T[7] + T[8 + c] * T[11]);

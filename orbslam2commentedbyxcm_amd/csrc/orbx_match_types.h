@@ -123,6 +123,7 @@ struct LocalArgs {
     const uint8_t* bad;        // [nmp] or null
     const int32_t* local_off;  // [B+1] frame b's local map = local_ids[local_off[b] .. local_off[b+1])
     const int32_t* local_ids;
+    int max_points, max_total; // a frame's range is clamped into both (a host local_off: its own maximum and total)
     float th;                  // SearchByProjection th
     float cos_limit;           // IsInFrustum viewingCosLimit
     int32_t* frame_mp;         // [B][cap] in/out: mvpMapPoints as MapPoint ids

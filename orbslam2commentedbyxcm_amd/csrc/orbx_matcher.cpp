@@ -891,18 +891,33 @@ int orbx_match_sequence_device_ex(orbx_matcher* m, const orbx_sequence* sq, void
     return ORBX_OK;
 }
 
-// Tracking::SearchLocalPoints for a batch of Frames in HBM (see include/orbx.h)
-int orbx_search_local_points_device(orbx_matcher* m, const orbx_mappoints_device* mps,
-                                    const orbx_local_map_batch* lm, void* stream) {
+namespace {
+
+// What orbx_search_local_points_device and orbx_search_local_points_offsets_device check alike.
+int check_local_points(const orbx_matcher* m, const orbx_mappoints_device* mps, const orbx_local_map_batch* lm, bool host_off) {
     if (!m || !mps || !lm) return fail(ORBX_ERR_ARG, "null argument");
     const int B = lm->batch, cap = lm->cap, nlevels = lm->nlevels;
-    if (B < 0 || cap <= 0 || cap >= 8192 || !lm->scale_factors || nlevels < 2 || nlevels > 32 || !lm->local_off)
+    if (B < 0 || cap <= 0 || cap >= 8192 || !lm->scale_factors || nlevels < 2 || nlevels > 32 || (host_off && !lm->local_off))
         return fail(ORBX_ERR_ARG, "bad argument");
     if (B == 0) return ORBX_OK;
     if (!lm->kps || !lm->desc || !lm->n || !lm->Tcw || !lm->frame_mp || !lm->nmatches || !mps->pos || !mps->desc ||
         !mps->normal || !mps->max_distance || !mps->min_distance || !mps->observations)
         return fail(ORBX_ERR_ARG, "null buffer");
     if (mps->n < 0 || mps->n >= kMaxMapPointIds) return fail(ORBX_ERR_ARG, "MapPoint table of 2^30 or more");
+    return ORBX_OK;
+}
+
+int search_local_points(orbx_matcher* m, const orbx_mappoints_device* mps, const orbx_local_map_batch* lm,
+                        const int32_t* d_local_off, int maxnq, int total, void* stream);
+
+}  // namespace
+
+// Tracking::SearchLocalPoints for a batch of Frames in HBM (see include/orbx.h)
+int orbx_search_local_points_device(orbx_matcher* m, const orbx_mappoints_device* mps,
+                                    const orbx_local_map_batch* lm, void* stream) {
+    const int rc = check_local_points(m, mps, lm, true);
+    if (rc || lm->batch == 0) return rc;
+    const int B = lm->batch;
     int maxnq = 0;
     for (int b = 0; b < B; b++) {
         const int c = lm->local_off[b + 1] - lm->local_off[b];
@@ -912,6 +927,30 @@ int orbx_search_local_points_device(orbx_matcher* m, const orbx_mappoints_device
     const int total = lm->local_off[B];
     if (maxnq > (1 << 20)) return fail(ORBX_ERR_ARG, "a local map of more than 2^20 MapPoints");
     if (total > 0 && !lm->local_ids) return fail(ORBX_ERR_ARG, "null local_ids");
+    return search_local_points(m, mps, lm, nullptr, maxnq, total, stream);
+}
+
+// The same with the offsets in HBM, as orbx_update_local_map_device wrote them
+int orbx_search_local_points_offsets_device(orbx_matcher* m, const orbx_mappoints_device* mps,
+                                            const orbx_local_map_batch* lm, const int32_t* d_local_off,
+                                            int max_local_points, int max_total, void* stream) {
+    const int rc = check_local_points(m, mps, lm, false);
+    if (rc) return rc;
+    if (max_local_points < 0 || max_total < 0) return fail(ORBX_ERR_ARG, "negative size");
+    if (lm->batch == 0) return ORBX_OK;
+    if (!d_local_off) return fail(ORBX_ERR_ARG, "null local_off");
+    if (max_local_points > (1 << 20)) return fail(ORBX_ERR_ARG, "a local map of more than 2^20 MapPoints");
+    if (max_total > 0 && !lm->local_ids) return fail(ORBX_ERR_ARG, "null local_ids");
+    return search_local_points(m, mps, lm, d_local_off, std::min(max_local_points, max_total), max_total, stream);
+}
+
+namespace {
+
+// The body of both: d_local_off null = lm->local_off from the host, checked by the caller, whose
+// maximum and total are then maxnq and total; else the device array, clamped into them.
+int search_local_points(orbx_matcher* m, const orbx_mappoints_device* mps, const orbx_local_map_batch* lm,
+                        const int32_t* d_local_off, int maxnq, int total, void* stream) {
+    const int B = lm->batch, cap = lm->cap, nlevels = lm->nlevels;
     // grids hold a frame's keypoints (cap < 8192, 13-bit sorted positions); the queries
     // (local MapPoints) are not position-encoded, so a local map may exceed that
     HIP_TRY(hipSetDevice(m->device));
@@ -932,12 +971,14 @@ int orbx_search_local_points_device(orbx_matcher* m, const orbx_mappoints_device
     auto* d_scr = (unsigned long long*)(p + o_scr);
     auto* d_loff = (int32_t*)(p + o_loff);
     auto* d_grids = grids ? (unsigned char*)(p + o_grids) : nullptr;
-    char* h = nullptr;
-    int slot = 0;
-    HIP_TRY(m->stage.get(sizeof(int32_t) * (B + 1), &h, &slot));
-    std::memcpy(h, lm->local_off, sizeof(int32_t) * (B + 1));
-    HIP_TRY(hipMemcpyAsync(d_loff, h, sizeof(int32_t) * (B + 1), hipMemcpyHostToDevice, s));
-    HIP_TRY(m->stage.copied(slot, s));
+    if (!d_local_off) {
+        char* h = nullptr;
+        int slot = 0;
+        HIP_TRY(m->stage.get(sizeof(int32_t) * (B + 1), &h, &slot));
+        std::memcpy(h, lm->local_off, sizeof(int32_t) * (B + 1));
+        HIP_TRY(hipMemcpyAsync(d_loff, h, sizeof(int32_t) * (B + 1), hipMemcpyHostToDevice, s));
+        HIP_TRY(m->stage.copied(slot, s));
+    }
     LocalArgs A{};
     A.kps = lm->kps;
     A.desc = lm->desc;
@@ -964,7 +1005,9 @@ int orbx_search_local_points_device(orbx_matcher* m, const orbx_mappoints_device
     A.max_distance = mps->max_distance;
     A.min_distance = mps->min_distance;
     A.bad = mps->bad;
-    A.local_off = d_loff;
+    A.local_off = d_local_off ? d_local_off : d_loff;
+    A.max_points = maxnq;
+    A.max_total = total;
     A.local_ids = lm->local_ids;
     A.th = lm->th;
     A.cos_limit = lm->viewing_cos_limit;
@@ -989,6 +1032,8 @@ int orbx_search_local_points_device(orbx_matcher* m, const orbx_mappoints_device
                                    m->footprint == 4, m->footprint == 5 ? d_grids : nullptr));
     return ORBX_OK;
 }
+
+}  // namespace
 
 int orbx_matcher_set_footprint(orbx_matcher* m, int small) {
     if (!m) return fail(ORBX_ERR_ARG, "null matcher");

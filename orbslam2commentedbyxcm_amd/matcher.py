@@ -479,6 +479,40 @@ class ORBmatcher:
         max_distance / min_distance (n,) f32, observations (n,) i32, optional bad (n,) u8;
         local_off (B + 1) host ints, d_local_ids device i32; d_frame_mp (B, cap) i32 in/out,
         d_nmatches (B,) i32 out.  Asynchronous."""
+        off = np.ascontiguousarray(local_off, dtype=np.int32)
+        if len(off) != d_desc.shape[0] + 1:
+            raise ValueError("local_off needs batch + 1 entries")
+        mv, q, keep = self._local_map_batch(mps, d_kps, d_desc, d_n, d_Tcw, d_local_ids, d_frame_mp, d_nmatches,
+                                            scale_factors, fx, fy, cx, cy, width, height, th, viewing_cos_limit, bf,
+                                            d_u_right)
+        q.local_off = off.ctypes.data_as(I32P)
+        s = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        L.check(L.lib().orbx_search_local_points_device(self._h, C.byref(mv), C.byref(q), s))
+
+    def search_local_points_offsets_device(self, mps: dict, d_kps, d_desc, d_n, d_Tcw, d_local_off, d_local_ids,
+                                           d_frame_mp, d_nmatches, scale_factors, fx, fy, cx, cy, width, height,
+                                           max_local_points: int, max_total: int | None = None, th: float = 1.0,
+                                           viewing_cos_limit: float = 0.5, bf: float = 0.0, d_u_right=None,
+                                           stream=None) -> None:
+        """orbx_search_local_points_offsets_device: search_local_points_device with local_off as a
+        device tensor (B + 1,) i32, as LocalMapTracker.update_local_map wrote it; scratch is sized
+        by max_total (default: the length of d_local_ids) and the launch by max_local_points.
+        Nothing is read back.  Asynchronous."""
+        if int(d_local_off.numel()) != int(d_desc.shape[0]) + 1:
+            raise ValueError("d_local_off needs batch + 1 entries")
+        mv, q, keep = self._local_map_batch(mps, d_kps, d_desc, d_n, d_Tcw, d_local_ids, d_frame_mp, d_nmatches,
+                                            scale_factors, fx, fy, cx, cy, width, height, th, viewing_cos_limit, bf,
+                                            d_u_right)
+        total = int(d_local_ids.numel()) if max_total is None else int(max_total)
+        s = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
+        L.check(L.lib().orbx_search_local_points_offsets_device(self._h, C.byref(mv), C.byref(q),
+                                                                C.c_void_p(d_local_off.data_ptr()),
+                                                                int(max_local_points), total, s))
+
+    @staticmethod
+    def _local_map_batch(mps, d_kps, d_desc, d_n, d_Tcw, d_local_ids, d_frame_mp, d_nmatches, scale_factors, fx, fy, cx,
+                         cy, width, height, th, viewing_cos_limit, bf, d_u_right):
+        """(orbx_mappoints_device, orbx_local_map_batch without local_off, what they point into)."""
         B, cap = d_desc.shape[0], d_desc.shape[1]
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         mv = L.MapPointsDevice()
@@ -487,9 +521,6 @@ class ORBmatcher:
         mv.max_distance, mv.min_distance = ptr(mps["max_distance"]), ptr(mps["min_distance"])
         mv.observations, mv.bad = ptr(mps["observations"]), ptr(mps.get("bad"))
         sf = _f32(scale_factors)
-        off = np.ascontiguousarray(local_off, dtype=np.int32)
-        if len(off) != B + 1:
-            raise ValueError("local_off needs batch + 1 entries")
         q = L.LocalMapBatch()
         q.batch, q.cap = B, cap
         q.kps, q.desc, q.n, q.u_right, q.Tcw = ptr(d_kps), ptr(d_desc), ptr(d_n), ptr(d_u_right), ptr(d_Tcw)
@@ -497,12 +528,10 @@ class ORBmatcher:
         q.min_x, q.max_x, q.min_y, q.max_y = 0.0, float(width), 0.0, float(height)
         q.nlevels = len(sf)
         q.scale_factors = sf.ctypes.data_as(F32P)
-        q.local_off = off.ctypes.data_as(I32P)
         q.local_ids = ptr(d_local_ids)
         q.th, q.viewing_cos_limit = th, viewing_cos_limit
         q.frame_mp, q.nmatches = ptr(d_frame_mp), ptr(d_nmatches)
-        s = None if stream is None else C.c_void_p(getattr(stream, "cuda_stream", stream))
-        L.check(L.lib().orbx_search_local_points_device(self._h, C.byref(mv), C.byref(q), s))
+        return mv, q, sf
 
     def set_timing(self, enable: bool = True) -> None:
         L.check(L.lib().orbx_matcher_set_timing(self._h, 1 if enable else 0))
