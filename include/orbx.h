@@ -1700,7 +1700,8 @@ int orbx_initializer_sets(int32_t* sets, int n, int iterations);
  * orbx_covis_erase_keyframe_device is the connection part of SetBadFlag (cc:506-508, 519-520):
  * EraseConnection(id) on every keyframe of id's row, each re-ordered if it held the entry, then
  * id's row and list are cleared.  Id 0 is a no-op.  mbNotErase, the children's new parents and
- * EraseObservation stay with the caller, who sets kf_bad and refreshes the observations.
+ * EraseObservation stay with the caller, who sets kf_bad and refreshes the observations;
+ * orbx_covis_set_bad_flag_device below is the whole of SetBadFlag.
  *
  * Rows in LDS: one workgroup counts a keyframe's connections in an LDS histogram while
  * max_keyframes <= ORBX_COVIS_LDS_KEYFRAMES (orbx_debug_set "covis_lds_keyframes" lowers the
@@ -1857,7 +1858,8 @@ int orbx_local_ba_apply_device(orbx_covis* g, const orbx_local_ba_apply* a, void
  *   not tested for badness -- a parent that was not yet local is appended and ends the whole
  *   walk (the reference's break leaves the outer loop).  The children of k are the keyframes c
  *   that are not bad and have parent[c] == k; `parent` is the graph's own array unless the
- *   caller passes one (after culling or a loop closure the caller owns the spanning tree);
+ *   caller passes one (orbx_covis_set_bad_flag_device and orbx_keyframe_culling_device keep the
+ *   graph's own array right through a cull; after a loop closure the caller owns the tree);
  *   ref_kf[b] = pKFmax when there is one;
  *   UpdateLocalPoints (cc:1354-1380): the local keyframes in list order, each row of the graph's
  *   cleaned table in index order (whether or not the keyframe is bad now), the first appearance
@@ -1926,13 +1928,96 @@ typedef struct {
 } orbx_track_local_map_tally;
 int orbx_track_local_map_tally_device(orbx_covis* g, const orbx_track_local_map_tally* t, void* stream);
 
+/* ---- LocalMapping::KeyFrameCulling, MapPointCulling and the full KeyFrame::SetBadFlag (§4.26) ----
+ * The map tables that the culls read and change, by device pointer.  kf_mp, kf_bad and mp_bad
+ * are the arrays of the graph's last orbx_covis_refresh_observations_device (the host form keeps
+ * a copy of its own: ORBX_ERR_ARG); the other tables are [n_keyframes][cap] beside kf_mp.  Every
+ * call below reads the graph's cleaned table, so a MapPoint named at two indices of a row counts
+ * once (a deviation: the reference's mvpMapPoints would count it twice in nMPs), and ends by
+ * running the observation refresh's launches on the mutated kf_mp: the observation CSR and the
+ * cleaned table the graph holds afterwards are those of a fresh refresh.
+ *
+ * orbx_keyframe_culling_device is LocalMapping::KeyFrameCulling (LocalMapping.cc:708-775) for the
+ * current keyframe cur_kf.  The candidates are its GetVectorCovisibleKeyFrames(), taken once in
+ * list order (cand, n_cand); id 0 is skipped (cc:718), and so is a keyframe that is bad already
+ * (outside the reference, whose lists hold none).  For each index of a candidate's cleaned row:
+ * NULL and bad MapPoints are skipped, unless monocular so is mvDepth > mThDepth || mvDepth < 0,
+ * every other entry counts into nMPs, and into nRedundantObservations when Observations() > 3
+ * (MapPoint.cc:134-146: an observation with mvuRight >= 0 counts 2) and at least 3 other
+ * observers have mvKeysUn[idx].octave <= scaleLevel + 1.  The candidate is culled when
+ * (double)nRedundantObservations > 0.9 * (double)nMPs.  SetBadFlag runs inside the loop, so later
+ * candidates are counted on the state it left.  cand_counts [max_conn][3] = {nMPs,
+ * nRedundantObservations, 0 | 1 culled | 2 only marked mbToBeErased}; culled [max_conn] in cull
+ * order, n_culled; n_new_bad_mp the MapPoints that went bad; status ORBX_CULL_STATUS_*.  One
+ * current keyframe per call: several calls on one graph at a time would race on the state that
+ * the reference serialises.
+ *
+ * orbx_covis_set_bad_flag_device is KeyFrame::SetBadFlag (KeyFrame.cc:492-598) on ids[0], ids[1],
+ * ... (a host array) in order, which is also what KeyFrame::SetErase (cc:476-489) runs once the
+ * caller cleared mbNotErase.  Id 0 returns (cc:497); kf_not_erase sets only kf_to_be_erased
+ * (cc:500-503); a keyframe that is bad already is left alone.  EraseConnection(this) on every
+ * keyframe of the row, each re-ordered, entries below 15 included, if it held the entry
+ * (cc:506-508, 607-620); EraseObservation(this) on every entry (cc:510-512, MapPoint.cc:152-180):
+ * when a MapPoint's nObs falls to <= 2 its own SetBadFlag runs (MapPoint.cc:195-212): mp_bad is
+ * set and its entry becomes -1 in every remaining observer, in kf_mp and in the graph's cleaned
+ * table; the culled keyframe's own row keeps its entries.  The row and list are cleared
+ * (cc:519-520).  The children (the keyframes that are not bad and have parent == id; not id's
+ * own parent, a cycle that the reference's tree cannot hold) get new
+ * parents (cc:522-584): sParentCandidates = {mpParent}; while children remain, the largest
+ * GetWeight over (child in ascending id) x (position in that child's ordered list) whose keyframe
+ * is a candidate -- strict >, the first in that order wins a tie --; that child's parent changes,
+ * it becomes a candidate; when a round finds nothing every remaining child gets mpParent.  The
+ * graph's own `parent` array is changed.  A culled keyframe whose parent is -1 is outside the
+ * reference (it dereferences NULL): children that find no candidate get -1 and status gets
+ * ORBX_CULL_STATUS_NO_PARENT.  kf_bad[id] = 1 (cc:592).  mTcp, Map::EraseKeyFrame and
+ * KeyFrameDatabase::erase stay with the caller.
+ *
+ * orbx_map_point_culling_device is LocalMapping::MapPointCulling (LocalMapping.cc:185-220) over
+ * recent[0 .. *n_recent) (mlpRecentAddedMapPoints; distinct ids), in order: a bad point (or an id
+ * outside the map) is dropped; GetFoundRatio() = (float)mp_found / (float)mp_visible < 0.25f (one
+ * correctly rounded float division; 0 / 0 does not compare less) -> SetBadFlag and drop;
+ * (int)cur_kf_id - mp_first_kf >= 2 && Observations() <= cnThObs (2 monocular, else 3) ->
+ * SetBadFlag and drop; a difference >= 3 -> drop; else kept.  The kept entries are compacted in
+ * order, *n_recent is rewritten, *n_culled counts the SetBadFlags.
+ *
+ * orbx_covis_observation_counts_device writes Observations() of every MapPoint from the
+ * observation CSR (0 for a bad one): what orbx_track_local_map_tally.observations takes.
+ *
+ * ORBX_ERR_ARG, decided before any device call: a null graph or required pointer, a negative
+ * max_recent, a call before any refresh, kf_bad / mp_bad that are not the arrays the graph kept,
+ * a graph last refreshed through the host form, an id outside the graph, a repeated id.  All
+ * pointers are device pointers unless noted; nothing is read back; asynchronous on `stream` (or
+ * the graph's own).  orbx_debug_set "cull_serial": the walk counts every candidate itself. */
+#define ORBX_CULL_STATUS_NO_PARENT 1
+typedef struct {
+    int32_t* kf_mp;                /* [n_keyframes][cap], in/out: the table of the last refresh */
+    uint8_t* kf_bad;               /* [n_keyframes] in/out; must be the array of the last refresh */
+    uint8_t* mp_bad;               /* [n_mappoints] in/out; likewise */
+    const orbx_keypoint* kf_keys_un; /* [n_keyframes][cap]: .octave is read (KeyFrameCulling only) */
+    const float* kf_u_right;       /* [n_keyframes][cap] mvuRight, NULL: every observation counts 1 */
+    const float* kf_depth;         /* [n_keyframes][cap] mvDepth; required unless monocular */
+    const float* kf_th_depth;      /* [n_keyframes] mThDepth; required unless monocular */
+    const uint8_t* kf_not_erase;   /* [n_keyframes] mbNotErase or NULL */
+    uint8_t* kf_to_be_erased;      /* [n_keyframes] mbToBeErased, in/out, or NULL */
+} orbx_map_tables;
+int orbx_keyframe_culling_device(orbx_covis* g, const orbx_map_tables* m, int cur_kf, int monocular,
+                                 int32_t* cand, int32_t* cand_counts, int32_t* n_cand, int32_t* culled,
+                                 int32_t* n_culled, int32_t* n_new_bad_mp, int32_t* status, void* stream);
+int orbx_covis_set_bad_flag_device(orbx_covis* g, const orbx_map_tables* m, const int32_t* ids /* host */, int Q,
+                                   int32_t* n_new_bad_mp, int32_t* status, void* stream);
+int orbx_map_point_culling_device(orbx_covis* g, const orbx_map_tables* m, int cur_kf_id, int monocular,
+                                  int32_t* recent, int32_t* n_recent, int max_recent, const int32_t* mp_first_kf,
+                                  const int32_t* mp_found, const int32_t* mp_visible, int32_t* n_culled, void* stream);
+int orbx_covis_observation_counts_device(orbx_covis* g, const float* kf_u_right, int32_t* out, void* stream);
+
 /* Alternative kernel forms and diagnostics switches, process-wide (tests and A/B tools;
  * the product reads no environment).  Names: "pz_seg" (pyramid levels per launch, 0 = one
  * launch), "pz_byte" (byte-read k_pyramid), "desc_tiles" (tile-major describe),
  * "extract_dma" (single host call through DMA copies), "replay_threads" (64..1024),
  * "dup_stage" (launch extraction stage k twice), "oct_stamps" / "call_stamps" /
  * "match_stamps" (phase stamps to stderr), "covis_lds_keyframes" (the covisibility graph's LDS
- * bound, read by orbx_covis_create), "essgraph_stamps" (orbx_optimize_essential_graph*:
+ * bound, read by orbx_covis_create), "cull_serial" (orbx_keyframe_culling_device without the
+ * speculative pass), "essgraph_stamps" (orbx_optimize_essential_graph*:
  * problem 0's wall-clock ticks in the linearisations and in the linear solves to stderr;
  * synchronises the stream).  value < 0 restores the default; name NULL
  * restores every default.  Every form gives the same results.  A frame size's plan reads

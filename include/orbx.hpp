@@ -272,6 +272,33 @@ public:
     void UpdateConnections(int id) { UpdateConnections(std::vector<int32_t>{id}); }
     // the connection part of pKF->SetBadFlag()
     void EraseKeyFrame(int id, void* stream = nullptr) { check(orbx_covis_erase_keyframe_device(h_, id, stream)); }
+    // pKF->SetBadFlag() for each of ids, in order, on the device tables of the last refresh (also
+    // SetErase() once the caller cleared mbNotErase): connections, observations, the MapPoints
+    // that fall to nObs <= 2, the children's new parents, mbBad.  The results are device ints.
+    void SetBadFlag(const orbx_map_tables& maps, const std::vector<int32_t>& ids, int32_t* d_nNewBadMapPoints,
+                    int32_t* d_status, void* stream = nullptr) {
+        check(orbx_covis_set_bad_flag_device(h_, &maps, ids.data(), (int)ids.size(), d_nNewBadMapPoints, d_status, stream));
+    }
+    // LocalMapping::KeyFrameCulling() for mpCurrentKeyFrame = curKF; every result is a device array
+    struct CullResult {
+        int32_t *cand, *candCounts, *nCand, *culled, *nCulled, *nNewBadMapPoints, *status;
+    };
+    void KeyFrameCulling(const orbx_map_tables& maps, int curKF, bool mbMonocular, const CullResult& r,
+                         void* stream = nullptr) {
+        check(orbx_keyframe_culling_device(h_, &maps, curKF, mbMonocular ? 1 : 0, r.cand, r.candCounts, r.nCand, r.culled,
+                                           r.nCulled, r.nNewBadMapPoints, r.status, stream));
+    }
+    // LocalMapping::MapPointCulling() over mlpRecentAddedMapPoints (d_recent / d_nRecent, in/out)
+    void MapPointCulling(const orbx_map_tables& maps, int nCurrentKFid, bool mbMonocular, int32_t* d_recent,
+                         int32_t* d_nRecent, int maxRecent, const int32_t* d_mnFirstKFid, const int32_t* d_mnFound,
+                         const int32_t* d_mnVisible, int32_t* d_nCulled, void* stream = nullptr) {
+        check(orbx_map_point_culling_device(h_, &maps, nCurrentKFid, mbMonocular ? 1 : 0, d_recent, d_nRecent, maxRecent,
+                                            d_mnFirstKFid, d_mnFound, d_mnVisible, d_nCulled, stream));
+    }
+    // MapPoint::Observations() of every MapPoint
+    void ObservationCounts(const float* d_mvuRight, int32_t* d_out, void* stream = nullptr) {
+        check(orbx_covis_observation_counts_device(h_, d_mvuRight, d_out, stream));
+    }
     // vector<KeyFrame*> GetVectorCovisibleKeyFrames(); weights: mvOrderedWeights
     std::vector<int32_t> GetVectorCovisibleKeyFrames(int id, std::vector<int32_t>* weights = nullptr) {
         std::vector<int32_t> kf((size_t)maxConn_), w((size_t)maxConn_);

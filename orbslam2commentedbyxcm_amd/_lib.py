@@ -71,6 +71,8 @@ EXPORTED = [
     "orbx_covis_read", "orbx_covis_refresh_observations", "orbx_local_ba_assemble_device", "orbx_local_ba_apply_device",
     "orbx_update_local_map_device", "orbx_update_local_map", "orbx_search_local_points_offsets_device",
     "orbx_track_local_map_tally_device",
+    "orbx_keyframe_culling_device", "orbx_covis_set_bad_flag_device", "orbx_map_point_culling_device",
+    "orbx_covis_observation_counts_device",
 ]
 
 ORBX_DEPTH_U16 = 0
@@ -339,6 +341,15 @@ class TrackLocalMapTally(C.Structure):
                 ("ok", C.c_void_p)]
 
 
+ORBX_CULL_STATUS_NO_PARENT = 1
+
+
+class MapTables(C.Structure):
+    """orbx_map_tables."""
+    _fields_ = [(k, C.c_void_p) for k in ("kf_mp", "kf_bad", "mp_bad", "kf_keys_un", "kf_u_right", "kf_depth",
+                                          "kf_th_depth", "kf_not_erase", "kf_to_be_erased")]
+
+
 # ---- handle lifetime (DESIGN.md §1 "Teardown") ------------------------------------
 # Every object that owns liborbx handles or HIP streams registers here.  At interpreter
 # exit the atexit hook synchronises the devices and closes them newest first -- while the
@@ -588,6 +599,11 @@ def lib() -> C.CDLL:
                                                           C.c_int, C.c_int, vp]
     L.orbx_track_local_map_tally_device.argtypes = [vp, C.POINTER(TrackLocalMapTally), vp]
     L.orbx_covis_ordered.argtypes = [vp, C.c_int, i32p, i32p, C.c_int, ip]
+    L.orbx_keyframe_culling_device.argtypes = [vp, C.POINTER(MapTables), C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbx_covis_set_bad_flag_device.argtypes = [vp, C.POINTER(MapTables), i32p, C.c_int, vp, vp, vp]
+    L.orbx_map_point_culling_device.argtypes = [vp, C.POINTER(MapTables), C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp,
+                                                vp, vp]
+    L.orbx_covis_observation_counts_device.argtypes = [vp, vp, vp, vp]
     L.orbx_version.restype = C.c_char_p
     L.orbx_device_count.argtypes = [ip]
     L.orbx_last_error.restype = C.c_char_p

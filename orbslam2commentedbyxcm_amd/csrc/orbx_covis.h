@@ -1,6 +1,6 @@
 // orbx_covis.h -- what the translation units that work on the covisibility graph share
-// (orbx_covis.hip, orbx_localmap.hip): the graph's device arrays, the handle, and the small
-// device helpers.  DESIGN.md 4.24, 4.25.
+// (orbx_covis.hip, orbx_localmap.hip, orbx_culling.hip): the graph's device arrays, the handle, the
+// small device helpers and the row helpers.  DESIGN.md 4.24, 4.25, 4.26.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@ namespace orbx {
 
 constexpr int kCvThreads = kSortThreads;
 constexpr int kCvWaves = kCvThreads / 64;
+constexpr int kCvTh = 15;  // KeyFrame.cc:362
 
 struct CovisDev {
     int K, cap, n, max_conn, dense_lds;  // dense_lds: the dense row lives in LDS
@@ -87,6 +88,106 @@ static __device__ int cv_block_scan(int v, int* s_w, int& total) {
     return before + inc - v;
 }
 
+struct CvScratch {
+    int w[kCvWaves];
+    int m, n15;
+    unsigned long long best;
+};
+
+// Entries, entries >= th and the maximum (the lowest id among equal weights: the strict > in
+// ascending id order, cc:370) of a dense row; then, unless it is empty or exceeds max_conn,
+// keyframe t's sparse row in ascending id.  Uniform over the workgroup.
+static __device__ void cv_dense_to_row(const CovisDev& D, int t, const int* dense, CvScratch& S, int& m, int& n15, int& kfmax) {
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        S.m = 0;
+        S.n15 = 0;
+        S.best = 0ull;
+    }
+    __syncthreads();
+    int lm = 0, l15 = 0;
+    unsigned long long lb = 0ull;
+    for (int k = tid; k < D.K; k += kCvThreads) {
+        const int w = cv_ld(dense + k);
+        if (w > 0) {
+            lm++;
+            l15 += w >= kCvTh;
+            const unsigned long long key = (unsigned long long)(unsigned)w << 32 | (0xFFFFFFFFu - (unsigned)k);
+            lb = key > lb ? key : lb;
+        }
+    }
+    if (lm) {
+        atomicAdd(&S.m, lm);
+        atomicAdd(&S.n15, l15);
+        atomicMax(&S.best, lb);
+    }
+    __syncthreads();
+    m = S.m;
+    n15 = S.n15;
+    kfmax = m ? (int)(0xFFFFFFFFu - (unsigned)(S.best & 0xFFFFFFFFull)) : -1;
+    if (m == 0 || m > D.max_conn) return;
+    int base = 0;
+    const size_t r0 = (size_t)t * D.max_conn;
+    for (int k0 = 0; k0 < D.K; k0 += kCvThreads) {
+        const int k = k0 + tid;
+        const int w = k < D.K ? cv_ld(dense + k) : 0;
+        int tot;
+        const int pos = cv_block_scan(w > 0, S.w, tot);
+        if (w > 0) {
+            D.row_kf[r0 + base + pos] = k;
+            D.row_w[r0 + base + pos] = w;
+        }
+        base += tot;
+    }
+    if (tid == 0) D.row_n[t] = m;
+    __syncthreads();
+}
+
+// Keyframe t's ordered list from its row of m entries: sort on (weight, id) and push_front =
+// weight descending, id descending among equal weights.  all: every entry (UpdateBestCovisibles);
+// else the entries >= th, or kfmax alone when there is none (UpdateConnections).  Returns the
+// list's front.  Uniform over the workgroup.
+static __device__ int cv_order_row(const CovisDev& D, int t, int m, bool all, int n15, int kfmax, unsigned long long* s_sort) {
+    const int tid = threadIdx.x;
+    int np = kSortThreads;
+    while (np < m) np <<= 1;
+    const int ne = np / kSortThreads;
+    const size_t r0 = (size_t)t * D.max_conn;
+    unsigned long long r[kSortPer];
+#pragma unroll
+    for (int e = 0; e < kSortPer; e++) {
+        r[e] = 0ull;
+        const int i = e * kSortThreads + tid;
+        if (e < ne && i < m) {
+            const int w = D.row_w[r0 + i], id = D.row_kf[r0 + i];
+            if (all || w >= kCvTh || (n15 == 0 && id == kfmax)) r[e] = (unsigned long long)(unsigned)w << 32 | (unsigned)id;
+        }
+    }
+    block_bitonic_sort64(r, ne, s_sort);
+    const int cnt = all ? m : (n15 > 0 ? n15 : 1);
+    for (int j = tid; j < cnt; j += kCvThreads) {
+        const unsigned long long key = s_sort[np - 1 - j];
+        D.ord_kf[r0 + j] = (int)(unsigned)(key & 0xFFFFFFFFull);
+        D.ord_w[r0 + j] = (int)(unsigned)(key >> 32);
+    }
+    const int front = (int)(unsigned)(s_sort[np - 1] & 0xFFFFFFFFull);
+    if (tid == 0) D.ord_n[t] = cnt;
+    __syncthreads();
+    return front;
+}
+
+// weight of keyframe id in keyframe q's row, 0 if absent
+__device__ __forceinline__ int cv_row_lookup(const CovisDev& D, int q, int id) {
+    const size_t r0 = (size_t)q * D.max_conn;
+    int lo = 0, hi = D.row_n[q];
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (D.row_kf[r0 + mid] < id) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < D.row_n[q] && D.row_kf[r0 + lo] == id ? D.row_w[r0 + lo] : 0;
+}
+
 }  // namespace orbx
 
 struct orbx_covis {
@@ -98,6 +199,8 @@ struct orbx_covis {
     std::vector<int32_t> h_ids;
     size_t lds = 0;
     bool refreshed = false;
+    bool host_form = false;       // the last refresh was the host form: the map is the graph's own copy
+    int32_t* cull_ws = nullptr;   // [2][K] the children and marks of SetBadFlag, allocated by the first cull
     orbx::AsmWs asm_ws{};  // allocated by the first assembly
     orbx::DeviceBuffer asm_batch;
     orbx::DeviceBuffer host_map;  // the host form's copy of the map

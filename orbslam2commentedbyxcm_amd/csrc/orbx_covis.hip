@@ -46,109 +46,8 @@
 namespace orbx {
 namespace {
 
-constexpr int kCvTh = 15;          // KeyFrame.cc:362
 constexpr int kCvGroups = 128;     // workgroups of a launch that takes a global dense row each
 constexpr int kCvMaxKeyframes = 1 << 20;
-
-struct CvScratch {
-    int w[kCvWaves];
-    int m, n15;
-    unsigned long long best;
-};
-
-// Entries, entries >= th and the maximum (the lowest id among equal weights: the strict > in
-// ascending id order, cc:370) of a dense row; then, unless it is empty or exceeds max_conn,
-// keyframe t's sparse row in ascending id.  Uniform over the workgroup.
-__device__ void cv_dense_to_row(const CovisDev& D, int t, const int* dense, CvScratch& S, int& m, int& n15, int& kfmax) {
-    const int tid = threadIdx.x;
-    if (tid == 0) {
-        S.m = 0;
-        S.n15 = 0;
-        S.best = 0ull;
-    }
-    __syncthreads();
-    int lm = 0, l15 = 0;
-    unsigned long long lb = 0ull;
-    for (int k = tid; k < D.K; k += kCvThreads) {
-        const int w = cv_ld(dense + k);
-        if (w > 0) {
-            lm++;
-            l15 += w >= kCvTh;
-            const unsigned long long key = (unsigned long long)(unsigned)w << 32 | (0xFFFFFFFFu - (unsigned)k);
-            lb = key > lb ? key : lb;
-        }
-    }
-    if (lm) {
-        atomicAdd(&S.m, lm);
-        atomicAdd(&S.n15, l15);
-        atomicMax(&S.best, lb);
-    }
-    __syncthreads();
-    m = S.m;
-    n15 = S.n15;
-    kfmax = m ? (int)(0xFFFFFFFFu - (unsigned)(S.best & 0xFFFFFFFFull)) : -1;
-    if (m == 0 || m > D.max_conn) return;
-    int base = 0;
-    const size_t r0 = (size_t)t * D.max_conn;
-    for (int k0 = 0; k0 < D.K; k0 += kCvThreads) {
-        const int k = k0 + tid;
-        const int w = k < D.K ? cv_ld(dense + k) : 0;
-        int tot;
-        const int pos = cv_block_scan(w > 0, S.w, tot);
-        if (w > 0) {
-            D.row_kf[r0 + base + pos] = k;
-            D.row_w[r0 + base + pos] = w;
-        }
-        base += tot;
-    }
-    if (tid == 0) D.row_n[t] = m;
-    __syncthreads();
-}
-
-// Keyframe t's ordered list from its row of m entries: sort on (weight, id) and push_front =
-// weight descending, id descending among equal weights.  all: every entry (UpdateBestCovisibles);
-// else the entries >= th, or kfmax alone when there is none (UpdateConnections).  Returns the
-// list's front.  Uniform over the workgroup.
-__device__ int cv_order_row(const CovisDev& D, int t, int m, bool all, int n15, int kfmax, unsigned long long* s_sort) {
-    const int tid = threadIdx.x;
-    int np = kSortThreads;
-    while (np < m) np <<= 1;
-    const int ne = np / kSortThreads;
-    const size_t r0 = (size_t)t * D.max_conn;
-    unsigned long long r[kSortPer];
-#pragma unroll
-    for (int e = 0; e < kSortPer; e++) {
-        r[e] = 0ull;
-        const int i = e * kSortThreads + tid;
-        if (e < ne && i < m) {
-            const int w = D.row_w[r0 + i], id = D.row_kf[r0 + i];
-            if (all || w >= kCvTh || (n15 == 0 && id == kfmax)) r[e] = (unsigned long long)(unsigned)w << 32 | (unsigned)id;
-        }
-    }
-    block_bitonic_sort64(r, ne, s_sort);
-    const int cnt = all ? m : (n15 > 0 ? n15 : 1);
-    for (int j = tid; j < cnt; j += kCvThreads) {
-        const unsigned long long key = s_sort[np - 1 - j];
-        D.ord_kf[r0 + j] = (int)(unsigned)(key & 0xFFFFFFFFull);
-        D.ord_w[r0 + j] = (int)(unsigned)(key >> 32);
-    }
-    const int front = (int)(unsigned)(s_sort[np - 1] & 0xFFFFFFFFull);
-    if (tid == 0) D.ord_n[t] = cnt;
-    __syncthreads();
-    return front;
-}
-
-// weight of keyframe id in keyframe q's row, 0 if absent
-__device__ __forceinline__ int cv_row_lookup(const CovisDev& D, int q, int id) {
-    const size_t r0 = (size_t)q * D.max_conn;
-    int lo = 0, hi = D.row_n[q];
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (D.row_kf[r0 + mid] < id) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < D.row_n[q] && D.row_kf[r0 + lo] == id ? D.row_w[r0 + lo] : 0;
-}
 
 __device__ __forceinline__ int* cv_dense(const CovisDev& D, unsigned long long* s_dyn) {
     return D.dense_lds ? (int*)(s_dyn + kSortMaxKeys) : D.ws + (size_t)blockIdx.x * D.K;
@@ -714,6 +613,7 @@ int orbx_covis_refresh_observations_device(orbx_covis* h, int n_keyframes, const
     D.kf_bad = kf_bad;
     D.mp_bad = mp_bad;
     h->refreshed = true;
+    h->host_form = false;
     HIP_TRY(hipMemsetAsync(D.obs_cnt, 0, (size_t)D.n * 4, s));
     if (n_keyframes > 0) {
         static thread_local bool attr = false;
@@ -757,9 +657,11 @@ int orbx_covis_refresh_observations(orbx_covis* h, int n_keyframes, const int32_
     if (nk) HIP_TRY(hipMemcpyAsync(p + o_n, kf_n, nk * 4, hipMemcpyHostToDevice, s));
     if (nk && kf_bad) HIP_TRY(hipMemcpyAsync(p + o_kb, kf_bad, nk, hipMemcpyHostToDevice, s));
     if (n_mappoints && mp_bad) HIP_TRY(hipMemcpyAsync(p + o_mb, mp_bad, (size_t)n_mappoints, hipMemcpyHostToDevice, s));
-    return orbx_covis_refresh_observations_device(h, n_keyframes, (const int32_t*)p, (const int32_t*)(p + o_n),
-                                                  kf_bad ? (const uint8_t*)(p + o_kb) : nullptr, n_mappoints,
-                                                  mp_bad ? (const uint8_t*)(p + o_mb) : nullptr, nullptr);
+    rc = orbx_covis_refresh_observations_device(h, n_keyframes, (const int32_t*)p, (const int32_t*)(p + o_n),
+                                                kf_bad ? (const uint8_t*)(p + o_kb) : nullptr, n_mappoints,
+                                                mp_bad ? (const uint8_t*)(p + o_mb) : nullptr, nullptr);
+    h->host_form = true;
+    return rc;
 }
 
 int orbx_covis_update_connections_device(orbx_covis* h, const int32_t* ids, int Q, void* stream) {

@@ -13,7 +13,7 @@ bool unloading();
 
 // Alternative kernel forms and diagnostics switches (orbx_runtime.cpp): the value set by
 // orbx_debug_set, else (debug builds only) the ORBX_* environment variable, else dflt.
-enum class Tune { PzSeg, PzByte, DescTiles, ExtractDma, ReplayThreads, DupStage, OctStamps, CallStamps, MatchStamps, EssgraphStamps, CovisLdsKeyframes };
+enum class Tune { PzSeg, PzByte, DescTiles, ExtractDma, ReplayThreads, DupStage, OctStamps, CallStamps, MatchStamps, EssgraphStamps, CovisLdsKeyframes, CullSerial };
 int tuning(Tune k, int dflt);
 // the environment variable `name` in a debug build (-DORBX_DEBUG=1), nullptr in the product
 const char* debug_env(const char* name);

@@ -43,6 +43,7 @@ constexpr Knob kKnobs[] = {
     {"match_stamps", "ORBX_MATCH_STAMPS"},     // batched matcher phase stamps (diagnostics)
     {"essgraph_stamps", "ORBX_ESSGRAPH_STAMPS"},  // k_essential_graph's linearisation / solve ticks (diagnostics)
     {"covis_lds_keyframes", "ORBX_COVIS_LDS_KEYFRAMES"},  // keyframes up to which a covisibility row is counted in LDS
+    {"cull_serial", "ORBX_CULL_SERIAL"},  // KeyFrameCulling without the speculative pass: the walk counts every candidate
 };
 constexpr int kNumKnobs = sizeof(kKnobs) / sizeof(kKnobs[0]);
 std::atomic<int> g_set[kNumKnobs];      // orbx_debug_set values
