@@ -1217,8 +1217,10 @@ int orbx_optimize_sim3(orbx_matcher* m, const orbx_optimize_sim3_batch* os);
  * launch: one persistent workgroup per problem runs optimize(5), the chi2 / depth test,
  * optimize(10) on the edges that passed and the final test.  The covisibility walk that
  * chooses the keyframes and points (cc:526-583) stays with the caller (or with
- * orbx_local_ba_assemble_device on a covisibility graph), as do the erasure of the flagged
- * observations (orbx_local_ba_apply_device) and UpdateNormalAndDepth (cc:828-853).  The stop flag (pbStopFlag)
+ * orbx_local_ba_assemble_device on a covisibility graph), as does the erasure of the flagged
+ * observations (orbx_local_ba_apply_device); the UpdateNormalAndDepth of the write-back
+ * (cc:828-853) is orbx_update_normal_and_depth_device over pt_id after a refresh of the
+ * observations.  The stop flag (pbStopFlag)
  * is not supported: bDoMore is always true.  Float inputs are widened to double, everything
  * after is double (but the two float intermediates of the stereo projection), outputs are
  * rounded to float once.  Every sum has a fixed shape (no floating-point atomics) and no
@@ -1306,7 +1308,10 @@ int orbx_local_bundle_adjustment(orbx_matcher* m, const orbx_local_ba_batch* lba
  * it.  DESIGN.md §4.23.  With the caller: which keyframes and points are good (bad ones are
  * not passed), whether the results go to SetPose / SetWorldPos or to mTcwGBA / mPosGBA (the
  * nLoopKF switch), the spanning-tree propagation of LoopClosing.cc:740-800,
- * ComputeSceneMedianDepth and the rescale of the initial map.
+ * ComputeSceneMedianDepth and the rescale of the initial map.  The UpdateNormalAndDepth that
+ * ends the write-back of a point when nLoopKF == 0 (cc:273, the CreateInitialMapMonocular path)
+ * is orbx_update_normal_and_depth_device on pt_pos_opt and kf_Tcw_opt once they are in the
+ * map's tables (§4.27).
  *   The tables are those of orbx_local_ba_batch, with the same rules for observations that
  *   are no edges (ORBX_GLOBAL_BA_STATUS_BAD_INDEX).  Edge order is point order, then the
  *   caller's order within a point (the reference's orders are pointer orders); the order of S
@@ -1390,10 +1395,13 @@ int orbx_global_ba_envelope(int n_kf, const uint8_t* kf_fixed, int n_pt, const i
  * factored by a block-envelope (skyline) LDL^T without pivoting in natural (mnId) order that
  * gives the bytes of the dense factorisation; only an exactly zero (or non-finite) pivot is
  * a failed solve, which is a rejected trial.  There is no cap on keyframes.  DESIGN.md §4.22.
- * Out of scope, with the caller: CorrectLoop's Sim3 propagation and first map-point
- * correction (LoopClosing.cc:488-571), UpdateConnections, SearchAndFuse,
- * UpdateNormalAndDepth and building the graph on the device (the global bundle adjustment
- * that follows is orbx_global_bundle_adjustment_batch_device above).
+ * Before it, CorrectLoop's Sim3 propagation and first map-point correction
+ * (LoopClosing.cc:482-571) are orbx_correct_loop_propagate_device and the graph is built on the
+ * device by orbx_essential_graph_assemble_device; after it, the UpdateNormalAndDepth of
+ * cc:1148 is orbx_update_normal_and_depth_device on pt_pos_opt and kf_Tcw_opt (all three
+ * below).  With the caller: SearchAndFuse's map mutation between the two and
+ * the write-back of the results into its map (the global bundle adjustment that follows is
+ * orbx_global_bundle_adjustment_batch_device above).
  *   Problem b owns rows kf_off[b] .. kf_off[b + 1] of the keyframe table (the good keyframes
  *   in ascending mnId), edge_off[b] .. of the edge table and pt_off[b] .. of the point table
  *   (offsets over the whole tables, ascending).  kf_Tcw is the pose that gives the
@@ -1812,7 +1820,8 @@ int orbx_local_ba_assemble_device(orbx_covis* g, const orbx_local_ba_assembly* a
  * assembled tables: kf_Tcw_opt of the keyframes that are not fixed goes to kf_pose through
  * kf_id, pt_pos_opt to mp_pos through pt_id, and for every erase[o] kf_mp[keyframe][keypoint]
  * = -1 (EraseMapPointMatch; erase or kf_mp NULL: skipped).  What EraseObservation does to a
- * point's nObs, reference keyframe and badness, and UpdateNormalAndDepth, stay with the caller.
+ * point's nObs, reference keyframe and badness stays with the caller; UpdateNormalAndDepth is
+ * orbx_update_normal_and_depth_device on the ids of pt_id, after a refresh of the observations.
  * Device pointers; asynchronous on `stream` (or the graph's). */
 typedef struct {
     int batch;
@@ -2009,6 +2018,193 @@ int orbx_map_point_culling_device(orbx_covis* g, const orbx_map_tables* m, int c
                                   int32_t* recent, int32_t* n_recent, int max_recent, const int32_t* mp_first_kf,
                                   const int32_t* mp_found, const int32_t* mp_visible, int32_t* n_culled, void* stream);
 int orbx_covis_observation_counts_device(orbx_covis* g, const float* kf_u_right, int32_t* out, void* stream);
+
+/* ---- MapPoint::UpdateNormalAndDepth in its general form, on the observation CSR (§4.27) ----
+ * MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:386-439) for the MapPoints ids[0 .. n_ids) (a
+ * device array), or for every MapPoint of the last refresh when ids is NULL: the call that
+ * LoopClosing::CorrectLoop (LoopClosing.cc:554), Optimizer::OptimizeEssentialGraph
+ * (Optimizer.cc:1148), the write-back of LocalBundleAdjustment (cc:828-853) and that of
+ * Optimizer::BundleAdjustment when nLoopKF == 0 (cc:273) end with.  Per point, on the observers that the graph's observation CSR holds (the
+ * keyframes that are not bad), in ascending keyframe id:
+ *   normal = the mean of (P - Ow_i) / |P - Ow_i|, Ow_i = -R^T t of kf_Tcw[i];
+ *   dist = |P - Ow_ref|, ref = mp_ref_kf[p] (mpRefKF is the caller's);
+ *   level = kf_keys_un[ref][index of ref among the point's observations].octave, clamped into
+ *   [0, nlevels); max_distance = dist * scale_factors[level]; min_distance = max_distance /
+ *   scale_factors[nlevels - 1].
+ * A bad point and a point without observations are left untouched (cc:393, 400).  If ref is not
+ * among the observers the reference's observations[pRefKF] inserts index 0: index 0 is read and
+ * *status gets ORBX_NORMAL_STATUS_REF_NOT_OBSERVER.  An id outside the MapPoints of the last
+ * refresh, or a ref outside its keyframes, leaves the point untouched and sets
+ * ORBX_NORMAL_STATUS_BAD_INDEX.  Float inputs are widened to double, everything after is double
+ * (one sum per point, in observer order: no floating-point atomics), the outputs are rounded to
+ * float once.  The reference's own arithmetic is float with cv::norm's double accumulation; the
+ * difference is within the tolerance that tests/correct_loop_spread.py measures.
+ * ORBX_ERR_ARG, decided before any device call: a null graph, struct, table or status, a
+ * negative n_ids, nlevels outside 1..32, a call before any refresh.  scale_factors is a host
+ * array; every other pointer is a device pointer; status is one int32 that the call rewrites.
+ * Nothing is read back; asynchronous on `stream` (or the graph's own). */
+#define ORBX_NORMAL_STATUS_REF_NOT_OBSERVER 1
+#define ORBX_NORMAL_STATUS_BAD_INDEX 2
+typedef struct {
+    const float* kf_Tcw;              /* [n_keyframes][12] rows 0..2 of GetPose() */
+    const orbx_keypoint* kf_keys_un;  /* [n_keyframes][cap]: .octave is read */
+    const int32_t* mp_ref_kf;         /* [n_mappoints] mpRefKF->mnId */
+    const float* mp_pos;              /* [n_mappoints][3] GetWorldPos() */
+    const float* scale_factors;       /* host: mvScaleFactors (nlevels) */
+    int nlevels;
+    float* normal;                    /* [n_mappoints][3] mNormalVector, in/out */
+    float* max_distance;              /* [n_mappoints] mfMaxDistance, in/out */
+    float* min_distance;              /* [n_mappoints] mfMinDistance, in/out */
+} orbx_normal_depth;
+int orbx_update_normal_and_depth_device(orbx_covis* g, const orbx_normal_depth* a, const int32_t* ids, int n_ids,
+                                        int32_t* status, void* stream);
+
+/* ---- LoopClosing::CorrectLoop: Sim3 propagation and the essential graph's assembly (§4.27) ----
+ * The two calls between orbx_optimize_sim3_batch_device and
+ * orbx_optimize_essential_graph_batch_device, on the graph and the map tables in HBM.  The
+ * keyframe id stands in for KeyFrame* wherever the reference iterates a map or set of pointers
+ * (§4.24).  Between the two calls the caller runs its fusion (SearchAndFuse, MapPoint::Replace:
+ * LoopClosing.cc:574-593) on kf_mp and refreshes the observations.  AddLoopEdge (cc:626-627), the
+ * propagation after the global bundle adjustment (cc:745-805) and DetectLoop's consistency groups
+ * stay with the caller.
+ *
+ * orbx_correct_loop_propagate_device is LoopClosing.cc:482-571 for mpCurrentKF = cur_kf:
+ *   a. UpdateConnections(cur_kf) (cc:482); conn = GetVectorCovisibleKeyFrames(cur_kf) in list
+ *      order without the keyframes that are bad (outside the reference, whose lists hold none) or
+ *      beyond the last refresh, then cur_kf (cc:488-489): conn[0 .. *n_conn).
+ *   b. mg2oScw is Scw (8 doubles: q xyzw, t, s), or, when Scw is NULL, Sim3(sim3_R, sim3_t,
+ *      sim3_s) * Sim3(Rmw, tmw, 1) of kf_Tcw[matched_kf] (cc:359-362; the layout of
+ *      orbx_optimize_sim3_batch.R12_opt / t12_opt / s12_opt of one candidate).  Per member i =
+ *      conn[j]: kf_Tcw_nc[j] = the bytes of kf_Tcw[i] (NonCorrectedSim3 = Sim3(Riw, tiw, 1));
+ *      corr_S[j] = CorrectedSim3 = Sim3(Ric, tic, 1) * Scw with Tic = Tiw * Twc formed in double
+ *      (the reference: a float cv::Mat product), Scw itself for cur_kf; kf_corr[i] = j, -1 for
+ *      every other keyframe of the graph.  These are orbx_essential_graph_batch's corr_S and the
+ *      source of its kf_corr.
+ *   c. cc:526-555 over the graph's cleaned rows.  The reference walks CorrectedSim3 in key order
+ *      and mnCorrectedByKF lets the first member that holds a point correct it: here the owner of
+ *      a point is the smallest member id among its observers (the observation CSR), and only the
+ *      thread of (owner, point) acts.  NULL entries, bad points and points whose input
+ *      mp_corrected_by_kf is cur_kf are skipped.  The owner writes mp_pos =
+ *      CorrectedSwi.map(Siw.map(P)) (rounded to float), mp_corrected_by_kf = cur_kf,
+ *      mp_corrected_ref = owner, and runs UpdateNormalAndDepth (above) on the state the reference
+ *      has at that moment: an observer that is a member with a smaller id than the owner has its
+ *      corrected pose already (SetPose runs after a member's points, cc:566), every other
+ *      observer its input pose.
+ *   d. kf_Tcw[i] = [R | t / s] of corr_S (cc:558-566), after all points; UpdateConnections of
+ *      every member (cc:570) as one batch.
+ * status (one int32, rewritten) gets the ORBX_NORMAL_STATUS_* bits of (c).
+ *
+ * orbx_essential_graph_assemble_device runs after the caller's fusion and refresh: it takes the
+ * first call's conn, n_conn, kf_corr and kf_Tcw_nc and writes the tables that
+ * orbx_essential_graph_batch takes for one problem.
+ *   1. LoopConnections (cc:595-618).  The reference walks the members in list order and takes
+ *      vpPreviousNeighbors = GetVectorCovisibleKeyFrames() of member i inside that loop, just
+ *      before UpdateConnections(i): LoopConnections[i] = (the keys of i's row afterwards) -
+ *      vpPreviousNeighbors - members.  Here each member's ordered list AND row are snapshot at
+ *      entry, then UpdateConnections runs on the members as one batch.  vpPreviousNeighbors of
+ *      member i is its ordered list at entry, unless the UpdateConnections of a member before it
+ *      in conn added or changed its entry in i's row (AddConnection, KeyFrame.cc:139-153: its
+ *      new weight w is >= 15 or i is its pKFmax, and w differs from the entry i's row held at
+ *      entry): UpdateBestCovisibles (cc:160-182) then re-ordered i's whole row, entries below 15
+ *      included, and vpPreviousNeighbors is every key of i's row at entry.  (Members that such
+ *      updates add are removed anyway.)  This gives the sets of the sequential walk
+ *      (tests/test_correct_loop_model.py).  Output: members in ascending id, each set in
+ *      ascending id, as the CSR lc_off[*n_conn + 1], lc_kf, lc_w (GetWeight after all updates),
+ *      lc_member.  conn, n_conn, kf_corr and kf_Tcw_nc must be the output of
+ *      orbx_correct_loop_propagate_device on this graph: the kernels index the graph's rows with
+ *      conn and only clamp the count.
+ *   2. Vertices: the keyframes of the last refresh that are not bad, ascending id: kf_ids[row],
+ *      kf_row[id] (-1 for a bad one; [max_keyframes]), *n_rows, *loop_row = kf_row[loop_kf],
+ *      kf_corr_rows[row] = kf_corr[id], kf_Tcw_rows[row] = kf_Tcw_nc of a member, the current
+ *      kf_Tcw otherwise.
+ *   3. Edges in the order of the Python package's essential_graph_edges: every kind-0 edge of
+ *      cc:954-986 over the LoopConnections CSR (the cur_kf - loop_kf pair is admitted below
+ *      min_feat), then per keyframe in ascending id its kind-1 edges (cc:989-1089): the parent
+ *      (the graph's `parent`), its loop edges to smaller ids (loop_off / loop_kf_ids: GetLoopEdges()
+ *      as a CSR over keyframe ids, ascending within a row), and the prefix of its ordered list
+ *      with weight >= min_feat without the parent, its children (the good keyframes whose parent
+ *      it is, §4.26), its loop edges, bad keyframes, ids not below its own and pairs inserted as
+ *      kind 0.  An edge to a keyframe without a row is dropped and sets BAD_KEYFRAME.  edge_v
+ *      holds rows; edge_off = {0, *n_edges}.  More edges than max_edges (or more LoopConnections
+ *      than max_lc): ORBX_ASSEMBLY_STATUS_CAPACITY, *n_edges (lc_off[*n_conn]) holds the need,
+ *      nothing is written past the capacity, and the edges are not written at all when the
+ *      LoopConnections did not fit.
+ *   4. pt_ref (cc:1125-1133) of every MapPoint of the last refresh: kf_row[mp_corrected_ref[p]]
+ *      where mp_corrected_by_kf[p] == cur_kf, else kf_row[mp_ref_kf[p]]; -1 for a bad point or a
+ *      reference outside the keyframes.  The optimiser leaves a point with pt_ref = -1 its input
+ *      bytes and reports ORBX_ESSENTIAL_GRAPH_STATUS_BAD_INDEX.  pt_off = {0, n_mappoints}.
+ *   5. *env_blocks = what orbx_essential_graph_envelope gives for these rows, loop_row and edges.
+ * The first assembly on a graph allocates its workspace: 3 (max_conn + 1) max_conn ints for the
+ * members' lists and rows at entry, and a few arrays of max_keyframes ints.
+ *
+ * ORBX_ERR_ARG, decided before any device call: a null graph, struct or required pointer, cur_kf
+ * / matched_kf / loop_kf outside the keyframes of the last refresh, a negative max_edges or
+ * max_lc, nlevels outside 1..32, a call before any refresh.  scale_factors is a host array;
+ * every other pointer is a device pointer.  Nothing is read back; no floating-point atomics; no
+ * workgroup waits on another; asynchronous on `stream` (or the graph's own). */
+typedef struct {
+    int cur_kf;
+    const double* Scw;             /* [8] mg2oScw, or NULL: composed from the four below */
+    const float* sim3_R;           /* [9] OptimizeSim3's R12_opt of the accepted candidate */
+    const float* sim3_t;           /* [3] t12_opt */
+    const float* sim3_s;           /* [1] s12_opt */
+    int matched_kf;                /* mpMatchedKF */
+    float* kf_Tcw;                 /* [n_keyframes][12] in/out */
+    float* mp_pos;                 /* [n_mappoints][3] in/out */
+    int32_t* mp_corrected_by_kf;   /* [n_mappoints] mnCorrectedByKF, in/out */
+    int32_t* mp_corrected_ref;     /* [n_mappoints] mnCorrectedReference, in/out */
+    const int32_t* mp_ref_kf;      /* [n_mappoints] */
+    const orbx_keypoint* kf_keys_un; /* [n_keyframes][cap] */
+    const float* scale_factors;    /* host (nlevels) */
+    int nlevels;
+    float* normal;                 /* [n_mappoints][3] in/out */
+    float* max_distance;           /* [n_mappoints] in/out */
+    float* min_distance;           /* [n_mappoints] in/out */
+    int32_t* conn;                 /* [max_conn + 1] out */
+    int32_t* n_conn;               /* [1] out */
+    double* corr_S;                /* [max_conn + 1][8] out */
+    int32_t* kf_corr;              /* [max_keyframes] out */
+    float* kf_Tcw_nc;              /* [max_conn + 1][12] out */
+    int32_t* status;               /* [1] out */
+} orbx_correct_loop_propagate;
+int orbx_correct_loop_propagate_device(orbx_covis* g, const orbx_correct_loop_propagate* a, void* stream);
+
+#define ORBX_ASSEMBLY_STATUS_CAPACITY 1
+#define ORBX_ASSEMBLY_STATUS_BAD_KEYFRAME 2
+typedef struct {
+    int cur_kf, loop_kf, min_feat; /* min_feat: 100 (Optimizer.cc:908) */
+    const int32_t* conn;           /* [max_conn + 1] of the propagation */
+    const int32_t* n_conn;         /* [1] */
+    const int32_t* kf_corr;        /* [max_keyframes] */
+    const float* kf_Tcw_nc;        /* [max_conn + 1][12] */
+    const float* kf_Tcw;           /* [n_keyframes][12] the current poses */
+    const int32_t* loop_off;       /* [n_keyframes + 1] GetLoopEdges() as a CSR */
+    const int32_t* loop_kf_ids;    /* [loop_off[n_keyframes]] ascending within a row */
+    const int32_t* mp_corrected_by_kf; /* [n_mappoints] */
+    const int32_t* mp_corrected_ref;   /* [n_mappoints] */
+    const int32_t* mp_ref_kf;      /* [n_mappoints] */
+    int max_lc, max_edges;
+    int32_t* lc_off;               /* [max_conn + 2] out */
+    int32_t* lc_member;            /* [max_conn + 1] out: the members, ascending id */
+    int32_t* lc_kf;                /* [max_lc] out */
+    int32_t* lc_w;                 /* [max_lc] out */
+    int32_t* kf_ids;               /* [n_keyframes] out */
+    int32_t* kf_row;               /* [max_keyframes] out */
+    int32_t* n_rows;               /* [1] out */
+    int32_t* kf_off;               /* [2] out: {0, *n_rows} */
+    int32_t* loop_row;             /* [1] out */
+    int32_t* kf_corr_rows;         /* [n_keyframes] out */
+    float* kf_Tcw_rows;            /* [n_keyframes][12] out */
+    int32_t* edge_v;               /* [max_edges][2] out */
+    int32_t* edge_kind;            /* [max_edges] out */
+    int32_t* n_edges;              /* [1] out */
+    int32_t* edge_off;             /* [2] out: {0, min(*n_edges, max_edges)} */
+    int32_t* pt_ref;               /* [n_mappoints] out */
+    int32_t* pt_off;               /* [2] out: {0, n_mappoints} */
+    int64_t* env_blocks;           /* [1] out */
+    int32_t* status;               /* [1] out: ORBX_ASSEMBLY_STATUS_* */
+} orbx_essential_graph_assembly;
+int orbx_essential_graph_assemble_device(orbx_covis* g, const orbx_essential_graph_assembly* a, void* stream);
 
 /* Alternative kernel forms and diagnostics switches, process-wide (tests and A/B tools;
  * the product reads no environment).  Names: "pz_seg" (pyramid levels per launch, 0 = one

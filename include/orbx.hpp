@@ -334,6 +334,34 @@ private:
     int maxConn_;
 };
 
+// LoopClosing::CorrectLoop on a Covisibility graph whose map tables live on the device
+// (src/LoopClosing.cc:482-571, 595-618; the tables of Optimizer::OptimizeEssentialGraph,
+// src/Optimizer.cc:913-1089, 1125-1133; MapPoint::UpdateNormalAndDepth, src/MapPoint.cc:386-439).
+// Every array of the structs is a device array except scale_factors; nothing is read back.
+class LoopClosing {
+public:
+    explicit LoopClosing(Covisibility& graph) : g_(graph) {}
+
+    // CorrectLoop() up to the fusion: UpdateConnections, the Sim3 propagation, the first
+    // correction of the MapPoints with their UpdateNormalAndDepth, SetPose, UpdateConnections
+    void CorrectLoopPropagate(const orbx_correct_loop_propagate& a, void* stream = nullptr) {
+        check(orbx_correct_loop_propagate_device(g_.handle(), &a, stream));
+    }
+    // after the caller's SearchAndFuse and RefreshObservations: LoopConnections and the tables of
+    // one orbx_essential_graph_batch problem
+    void AssembleEssentialGraph(const orbx_essential_graph_assembly& a, void* stream = nullptr) {
+        check(orbx_essential_graph_assemble_device(g_.handle(), &a, stream));
+    }
+    // pMP->UpdateNormalAndDepth() for d_ids[0 .. nIds), or for every MapPoint when d_ids is null
+    void UpdateNormalAndDepth(const orbx_normal_depth& a, const int32_t* d_ids, int nIds, int32_t* d_status,
+                              void* stream = nullptr) {
+        check(orbx_update_normal_and_depth_device(g_.handle(), &a, d_ids, nIds, d_status, stream));
+    }
+
+private:
+    Covisibility& g_;
+};
+
 // Tracking's local map (src/Tracking.cc:1342-1500) and TrackLocalMap's tally (cc:1047-1081) on a
 // Covisibility graph: frames are rows of a [frames][cap] MapPoint id table (-1 = NULL).
 class Tracking {

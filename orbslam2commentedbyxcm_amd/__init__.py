@@ -9,6 +9,7 @@ reference's ORBextractor / ORBmatcher interface.
 from ._lib import KEYPOINT_DTYPE, OrbxError, lib  # noqa: F401
 from .covisibility import CovisibilityGraph  # noqa: F401
 from .culling import MapCuller  # noqa: F401
+from .loopclosing import LoopCorrector  # noqa: F401
 from .database import KeyFrameDatabase  # noqa: F401
 from .extractor import ORBextractor  # noqa: F401
 from .initializer import Initializer  # noqa: F401
@@ -20,4 +21,4 @@ from .pnp import PnPsolver  # noqa: F401
 from .sim3 import Sim3Solver  # noqa: F401
 from .tracking import LocalMapTracker  # noqa: F401
 
-__all__ = ["ORBextractor", "CovisibilityGraph", "EssentialGraphOptimizer", "GlobalBundleAdjuster", "Initializer", "KeyFrameDatabase", "LocalBundleAdjuster", "LocalMapTracker", "MapCuller", "ORBmatcher", "PnPsolver", "PoseOptimizer", "Sim3Optimizer", "Sim3Solver", "Triangulator", "KEYPOINT_DTYPE", "OrbxError", "lib"]
+__all__ = ["ORBextractor", "CovisibilityGraph", "EssentialGraphOptimizer", "GlobalBundleAdjuster", "Initializer", "KeyFrameDatabase", "LocalBundleAdjuster", "LocalMapTracker", "LoopCorrector", "MapCuller", "ORBmatcher", "PnPsolver", "PoseOptimizer", "Sim3Optimizer", "Sim3Solver", "Triangulator", "KEYPOINT_DTYPE", "OrbxError", "lib"]

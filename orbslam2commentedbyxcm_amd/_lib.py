@@ -72,7 +72,8 @@ EXPORTED = [
     "orbx_update_local_map_device", "orbx_update_local_map", "orbx_search_local_points_offsets_device",
     "orbx_track_local_map_tally_device",
     "orbx_keyframe_culling_device", "orbx_covis_set_bad_flag_device", "orbx_map_point_culling_device",
-    "orbx_covis_observation_counts_device",
+    "orbx_covis_observation_counts_device", "orbx_update_normal_and_depth_device",
+    "orbx_correct_loop_propagate_device", "orbx_essential_graph_assemble_device",
 ]
 
 ORBX_DEPTH_U16 = 0
@@ -350,6 +351,43 @@ class MapTables(C.Structure):
                                           "kf_th_depth", "kf_not_erase", "kf_to_be_erased")]
 
 
+ORBX_NORMAL_STATUS_REF_NOT_OBSERVER = 1
+ORBX_NORMAL_STATUS_BAD_INDEX = 2
+
+
+class NormalDepth(C.Structure):
+    """orbx_normal_depth."""
+    _fields_ = [("kf_Tcw", C.c_void_p), ("kf_keys_un", C.c_void_p), ("mp_ref_kf", C.c_void_p), ("mp_pos", C.c_void_p),
+                ("scale_factors", C.POINTER(C.c_float)), ("nlevels", C.c_int), ("normal", C.c_void_p),
+                ("max_distance", C.c_void_p), ("min_distance", C.c_void_p)]
+
+
+class CorrectLoopPropagate(C.Structure):
+    """orbx_correct_loop_propagate."""
+    _fields_ = [("cur_kf", C.c_int), ("Scw", C.c_void_p), ("sim3_R", C.c_void_p), ("sim3_t", C.c_void_p),
+                ("sim3_s", C.c_void_p), ("matched_kf", C.c_int), ("kf_Tcw", C.c_void_p), ("mp_pos", C.c_void_p),
+                ("mp_corrected_by_kf", C.c_void_p), ("mp_corrected_ref", C.c_void_p), ("mp_ref_kf", C.c_void_p),
+                ("kf_keys_un", C.c_void_p), ("scale_factors", C.POINTER(C.c_float)), ("nlevels", C.c_int),
+                ("normal", C.c_void_p), ("max_distance", C.c_void_p), ("min_distance", C.c_void_p), ("conn", C.c_void_p),
+                ("n_conn", C.c_void_p), ("corr_S", C.c_void_p), ("kf_corr", C.c_void_p), ("kf_Tcw_nc", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
+ORBX_ASSEMBLY_STATUS_CAPACITY = 1
+ORBX_ASSEMBLY_STATUS_BAD_KEYFRAME = 2
+
+
+class EssentialGraphAssembly(C.Structure):
+    """orbx_essential_graph_assembly."""
+    _fields_ = ([("cur_kf", C.c_int), ("loop_kf", C.c_int), ("min_feat", C.c_int)] +
+                [(k, C.c_void_p) for k in ("conn", "n_conn", "kf_corr", "kf_Tcw_nc", "kf_Tcw", "loop_off", "loop_kf_ids",
+                                           "mp_corrected_by_kf", "mp_corrected_ref", "mp_ref_kf")] +
+                [("max_lc", C.c_int), ("max_edges", C.c_int)] +
+                [(k, C.c_void_p) for k in ("lc_off", "lc_member", "lc_kf", "lc_w", "kf_ids", "kf_row", "n_rows", "kf_off",
+                                           "loop_row", "kf_corr_rows", "kf_Tcw_rows", "edge_v", "edge_kind", "n_edges",
+                                           "edge_off", "pt_ref", "pt_off", "env_blocks", "status")])
+
+
 # ---- handle lifetime (DESIGN.md §1 "Teardown") ------------------------------------
 # Every object that owns liborbx handles or HIP streams registers here.  At interpreter
 # exit the atexit hook synchronises the devices and closes them newest first -- while the
@@ -604,6 +642,9 @@ def lib() -> C.CDLL:
     L.orbx_map_point_culling_device.argtypes = [vp, C.POINTER(MapTables), C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp,
                                                 vp, vp]
     L.orbx_covis_observation_counts_device.argtypes = [vp, vp, vp, vp]
+    L.orbx_update_normal_and_depth_device.argtypes = [vp, C.POINTER(NormalDepth), vp, C.c_int, vp, vp]
+    L.orbx_correct_loop_propagate_device.argtypes = [vp, C.POINTER(CorrectLoopPropagate), vp]
+    L.orbx_essential_graph_assemble_device.argtypes = [vp, C.POINTER(EssentialGraphAssembly), vp]
     L.orbx_version.restype = C.c_char_p
     L.orbx_device_count.argtypes = [ip]
     L.orbx_last_error.restype = C.c_char_p

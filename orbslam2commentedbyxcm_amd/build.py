@@ -27,7 +27,7 @@ LIB = PKG / "liborbx.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("ORBX_ARCH", "gfx950")
 
-SOURCES = ["orbx_geometry.cpp", "orbx_extract.hip", "orbx_match.hip", "orbx_api.cpp", "orbx_matcher.cpp", "orbx_vocab.hip", "orbx_bow.hip", "orbx_frame.hip", "orbx_fuse.hip", "orbx_kfdb.hip", "orbx_poseopt.hip", "orbx_sim3.hip", "orbx_pnp.hip", "orbx_optsim3.hip", "orbx_localba.hip", "orbx_globalba.hip", "orbx_essgraph.hip", "orbx_triangulate.hip", "orbx_initializer.hip", "orbx_covis.hip", "orbx_localmap.hip", "orbx_culling.hip", "orbx_runtime.cpp"]
+SOURCES = ["orbx_geometry.cpp", "orbx_extract.hip", "orbx_match.hip", "orbx_api.cpp", "orbx_matcher.cpp", "orbx_vocab.hip", "orbx_bow.hip", "orbx_frame.hip", "orbx_fuse.hip", "orbx_kfdb.hip", "orbx_poseopt.hip", "orbx_sim3.hip", "orbx_pnp.hip", "orbx_optsim3.hip", "orbx_localba.hip", "orbx_globalba.hip", "orbx_essgraph.hip", "orbx_triangulate.hip", "orbx_initializer.hip", "orbx_covis.hip", "orbx_localmap.hip", "orbx_culling.hip", "orbx_correctloop.hip", "orbx_runtime.cpp"]
 HEADERS = ["orbx_sincos.h", "orbx_block_sort.h", "orbx_geometry.h", "orbx_kernels.h", "orbx_match_types.h", "orbx_error.h", "orb_pattern.inc", "orbx_gmem.h", "orbx_rot_hist.h", "orbx_lm.h", "orbx_jacobi4.h", "orbx_epnp.h", "orbx_layout.h", "orbx_host.h", "orbx_sim3.h", "orbx_ba_edge.h", "orbx_envelope.h", "orbx_covis.h"]
 FLAGS = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
          f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",

@@ -1,6 +1,6 @@
 // orbx_covis.h -- what the translation units that work on the covisibility graph share
-// (orbx_covis.hip, orbx_localmap.hip, orbx_culling.hip): the graph's device arrays, the handle, the
-// small device helpers and the row helpers.  DESIGN.md 4.24, 4.25, 4.26.
+// (orbx_covis.hip, orbx_localmap.hip, orbx_culling.hip, orbx_correctloop.hip): the graph's device
+// arrays, the handle, the small device helpers and the row helpers.  DESIGN.md 4.24 - 4.27.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -201,6 +201,8 @@ struct orbx_covis {
     bool refreshed = false;
     bool host_form = false;       // the last refresh was the host form: the map is the graph's own copy
     int32_t* cull_ws = nullptr;   // [2][K] the children and marks of SetBadFlag, allocated by the first cull
+    float* cl_pose_ws = nullptr;  // [max_conn + 1][12] CorrectLoop's corrected poses, allocated by the first propagation
+    int32_t* eg_ws = nullptr;     // the essential graph assembly's workspace, allocated by the first assembly
     orbx::AsmWs asm_ws{};  // allocated by the first assembly
     orbx::DeviceBuffer asm_batch;
     orbx::DeviceBuffer host_map;  // the host form's copy of the map
@@ -219,5 +221,9 @@ inline int covis_enter(orbx_covis* h, void* stream, hipStream_t* s) {
     h->last = *s;
     return ORBX_OK;
 }
+
+// KeyFrame::UpdateConnections of the keyframes d_ids[0 .. min(*d_n, max_q)): distinct ids inside the
+// graph, ids and count on the device (orbx_covis.hip); the caller has entered the graph on s
+int covis_update_ids_device(orbx_covis* h, const int32_t* d_ids, const int32_t* d_n, int max_q, hipStream_t s);
 
 }  // namespace orbx

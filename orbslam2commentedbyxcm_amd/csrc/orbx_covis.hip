@@ -20,7 +20,8 @@
 //   k_covis_fill   one thread per slot: the observers of a point in arrival order (atomic cursor)
 //   k_covis_rank   one thread per slot: its rank among the point's observers by keyframe id is
 //                  its place in the segment
-// UpdateConnections (two launches):
+// UpdateConnections (two launches; the batch's ids come from the host, or, for CorrectLoop's
+// members, ids and count stay on the device):
 //   k_covis_update one workgroup per query keyframe: histogram over keyframe ids -- in LDS when
 //                  max_keyframes <= the bound (ORBX_COVIS_LDS_KEYFRAMES, "covis_lds_keyframes"),
 //                  else in a zeroed global row --, compaction to the sparse row, the thresholded
@@ -132,10 +133,11 @@ __global__ void k_covis_rank(CovisDev D) {
     D.obs_idx[o0 + rank] = i;
 }
 
-__global__ __launch_bounds__(kCvThreads) void k_covis_update(CovisDev D, const int32_t* ids, int Q) {
+__global__ __launch_bounds__(kCvThreads) void k_covis_update(CovisDev D, const int32_t* ids, int Q, const int32_t* d_Q) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long s_dyn[];
     __shared__ CvScratch S;
     const int tid = threadIdx.x;
+    if (d_Q) Q = clampi(*d_Q, 0, Q);  // the batch's size lives on the device
     int* dense = cv_dense(D, s_dyn);
     for (int b = blockIdx.x; b < Q; b += gridDim.x) {
         const int q = ids[b];
@@ -175,10 +177,11 @@ __global__ __launch_bounds__(kCvThreads) void k_covis_update(CovisDev D, const i
     }
 }
 
-__global__ __launch_bounds__(kCvThreads) void k_covis_merge(CovisDev D, const int32_t* ids, int Q) {
+__global__ __launch_bounds__(kCvThreads) void k_covis_merge(CovisDev D, const int32_t* ids, int Q, const int32_t* d_Q) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long s_dyn[];
     __shared__ CvScratch S;
     const int tid = threadIdx.x;
+    if (d_Q) Q = clampi(*d_Q, 0, Q);
     int* dense = cv_dense(D, s_dyn);
     for (int t = blockIdx.x; t < D.K; t += gridDim.x) {
         if (D.fresh[t]) continue;
@@ -519,7 +522,33 @@ int set_lds(K kern, size_t lds) {
 
 int dense_grid(const orbx_covis* h, int items) { return h->D.dense_lds ? items : std::min(items, kCvGroups); }
 
+// UpdateConnections of the Q keyframes ids[] (a device array; at most *d_Q of them when d_Q is given)
+int launch_update(orbx_covis* h, const int32_t* ids, int Q, const int32_t* d_Q, hipStream_t s) {
+    const CovisDev& D = h->D;
+    HIP_TRY(hipMemsetAsync(D.fresh, 0, (size_t)D.K, s));
+    static thread_local bool attr = false;
+    if (!attr) {
+        const size_t most = (size_t)kSortMaxKeys * 8 + (size_t)ORBX_COVIS_LDS_KEYFRAMES * 4;
+        int rc;
+        if ((rc = set_lds(k_covis_update, most)) || (rc = set_lds(k_covis_merge, most))) return rc;
+        attr = true;
+    }
+    k_covis_update<<<dense_grid(h, Q), kCvThreads, h->lds, s>>>(D, ids, Q, d_Q);
+    HIP_TRY(hipGetLastError());
+    k_covis_merge<<<dense_grid(h, D.K), kCvThreads, h->lds, s>>>(D, ids, Q, d_Q);
+    HIP_TRY(hipGetLastError());
+    return ORBX_OK;
+}
+
 }  // namespace
+
+namespace orbx {
+
+int covis_update_ids_device(orbx_covis* h, const int32_t* d_ids, const int32_t* d_n, int max_q, hipStream_t s) {
+    return max_q > 0 ? launch_update(h, d_ids, max_q, d_n, s) : ORBX_OK;
+}
+
+}  // namespace orbx
 
 extern "C" {
 
@@ -679,22 +708,10 @@ int orbx_covis_update_connections_device(orbx_covis* h, const int32_t* ids, int 
     hipStream_t s;
     int rc = covis_enter(h, stream, &s);
     if (rc) return rc;
-    const CovisDev& D = h->D;
     h->h_ids.swap(sorted);
     // pageable source: staged by the runtime before the call returns
     HIP_TRY(hipMemcpyAsync(h->ids, h->h_ids.data(), (size_t)Q * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(D.fresh, 0, (size_t)D.K, s));
-    static thread_local bool attr = false;
-    if (!attr) {
-        const size_t most = (size_t)kSortMaxKeys * 8 + (size_t)ORBX_COVIS_LDS_KEYFRAMES * 4;
-        if ((rc = set_lds(k_covis_update, most)) || (rc = set_lds(k_covis_merge, most))) return rc;
-        attr = true;
-    }
-    k_covis_update<<<dense_grid(h, Q), kCvThreads, h->lds, s>>>(D, h->ids, Q);
-    HIP_TRY(hipGetLastError());
-    k_covis_merge<<<dense_grid(h, D.K), kCvThreads, h->lds, s>>>(D, h->ids, Q);
-    HIP_TRY(hipGetLastError());
-    return ORBX_OK;
+    return launch_update(h, h->ids, Q, nullptr, s);
 }
 
 int orbx_covis_erase_keyframe_device(orbx_covis* h, int id, void* stream) {

@@ -593,7 +593,8 @@ class EssentialGraphOptimizer(PoseOptimizer):
     """Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:873-1150) on the GPU
     (csrc/orbx_essgraph.hip): OptimizeEssentialGraph for one map on host arrays and
     essential_graph_batch_device for B maps in HBM.  CorrectLoop's Sim3 propagation, the graph's
-    assembly (essential_graph_edges) and the updates after it stay with the caller.  The handle,
+    assembly on the device and UpdateNormalAndDepth after it are LoopCorrector's (loopclosing.py);
+    essential_graph_edges below is the host assembly.  The handle,
     close() and last_call_us() are PoseOptimizer's."""
 
     def OptimizeEssentialGraph(self, kf_Tcw, kf_corr, corr_S, loop_kf, edge_v, edge_kind, pt_pos, pt_ref,
