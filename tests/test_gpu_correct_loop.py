@@ -40,7 +40,10 @@ def lds_bound(request, orbx_built):
 class Dev:
     """A scene in HBM with the device graph after UpdateConnections of every keyframe."""
 
-    def __init__(self, name):
+    def __init__(self, name, io=None, decoy=None):
+        """io: a stream_order I/O object for the state's uploads (default: blocking ones); decoy:
+        the state (decoy_state) that is in place until an ordered run's real uploads.  The map
+        tables, which the graph is built from here, are the real ones either way."""
         import torch
 
         from orbslam2commentedbyxcm_amd import CovisibilityGraph, LoopCorrector
@@ -53,10 +56,12 @@ class Dev:
         keys = np.zeros((K, cap), L.KEYPOINT_DTYPE)
         keys["octave"] = st["octave"]
         self.kf_mp, self.kf_n, self.kf_bad, self.mp_bad = t(sc["kf_mp"]), t(sc["kf_n"]), t(sc["kf_bad"]), t(sc["mp_bad"])
-        self.d = {"kf_Tcw": t(st["poses"]), "mp_pos": t(st["mp_pos"]), "mp_corrected_by_kf": t(st["mp_corrected_by_kf"]),
+        ds = st if decoy is None else decoy
+        up = (lambda k: t(st[k])) if io is None else (lambda k: io.up(st[k], ds[k]))
+        self.d = {"kf_Tcw": up("poses"), "mp_pos": up("mp_pos"), "mp_corrected_by_kf": t(st["mp_corrected_by_kf"]),
                   "mp_corrected_ref": t(st["mp_corrected_ref"]), "mp_ref_kf": t(st["mp_ref_kf"]),
-                  "kf_keys_un": t(keys.view(np.uint8).reshape(K, cap, 28)), "normal": t(st["normal"]),
-                  "max_distance": t(st["max_distance"]), "min_distance": t(st["min_distance"])}
+                  "kf_keys_un": t(keys.view(np.uint8).reshape(K, cap, 28)), "normal": up("normal"),
+                  "max_distance": up("max_distance"), "min_distance": up("min_distance")}
         torch.cuda.synchronize()
         self.refresh()
         self.g.update_connections(list(range(K)))
@@ -94,6 +99,93 @@ class Dev:
         self.lc.assemble(self.sc["loop"], self.loop_off, self.loop_ids, self.sc["min_feat"], **kw)
         torch.cuda.synchronize()
         return self.lc.state()
+
+
+STATE_PAYLOAD = ("poses", "mp_pos", "normal", "max_distance", "min_distance")
+CHAIN_KEYS = ("conn", "n_conn", "corr_S", "kf_corr", "kf_Tcw_nc", "propagate_status", "kf_Tcw", "mp_pos", "normal",
+              "max_distance", "min_distance", "mp_corrected_by_kf", "mp_corrected_ref", "kf_ids", "n_rows", "edge_v",
+              "edge_kind", "n_edges", "pt_ref", "assemble_status", "kf_Tcw_opt", "pt_pos_opt", "Scw_opt", "trace", "chi2",
+              "status", "nd_status")
+
+
+def decoy_state(name):
+    """(state, Scw) of the scene with the same ids, octaves and reference keyframes; poses,
+    positions, normals, distances and the corrected Sim3 moved."""
+    sc, st = M.scene(name)
+    d = dict(st)
+    d["poses"] = np.array(st["poses"], np.float32, copy=True)
+    d["poses"][:, [3, 7, 11]] += np.float32([0.03, -0.02, 0.01])
+    d["mp_pos"] = (st["mp_pos"] + np.float32([0.02, 0.03, -0.01])).astype(np.float32)
+    d["normal"] = np.ascontiguousarray(st["normal"][:, ::-1]) + np.float32(0.125)
+    d["max_distance"] = (st["max_distance"] * np.float32(1.25) + np.float32(0.5)).astype(np.float32)
+    d["min_distance"] = (st["min_distance"] * np.float32(0.75) + np.float32(0.25)).astype(np.float32)
+    Scw = np.array(sc["Scw"], np.float64, copy=True)
+    Scw[4:7] += [0.05, -0.02, 0.03]
+    return d, Scw
+
+
+def run_chain(name, opt, io=None, decoy=False, decoy_only=False, env_blocks=None):
+    """The CorrectLoop chain on one stream with nothing read back: propagate -> refresh (on the
+    fused map) -> essential-graph assembly -> OptimizeEssentialGraph -> UpdateNormalAndDepth of
+    every point at the optimised positions.  A fresh graph per run (propagation changes it).
+    io: a stream_order I/O object (default: blocking uploads, a device synchronise around the
+    calls); decoy: the decoy state is in place before an ordered run's real uploads; decoy_only:
+    run on the decoy state.  env_blocks None: read back after the assembly (a synchronisation)."""
+    import stream_order as SO
+    sc, st = M.scene(name)
+    dst, dScw = decoy_state(name)
+    d = Dev(name, io=io, decoy=dst if decoy else None) if not decoy_only else None
+    if decoy_only:
+        d = Dev(name)
+        for k_dev, k_st in (("kf_Tcw", "poses"), ("mp_pos", "mp_pos"), ("normal", "normal"),
+                            ("max_distance", "max_distance"), ("min_distance", "min_distance")):
+            d.d[k_dev].copy_(d.t(dst[k_st]))
+    io = io or SO.SyncIO(d.dev)
+    Scw = np.asarray(sc["Scw"], np.float64)
+    d_Scw = io.up(dScw if decoy_only else Scw, dScw if decoy else None)
+    d_fused = io.up(sc["kf_mp_fused"])
+    io.begin()
+    with io.on_stream():
+        p = d.lc.propagate(sc["cur"], Scw=d_Scw, stream=io.stream)
+        io.end()
+        d.g.refresh_observations(d_fused, d.kf_n, d.kf_bad, d.mp_bad, stream=io.stream)
+        io.end()
+        a = d.lc.assemble(sc["loop"], d.loop_off, d.loop_ids, sc["min_feat"], stream=io.stream)
+        io.end()
+        if env_blocks is None:
+            env_blocks = max(1, int(a["env_blocks"].cpu()[0]))
+        o = d.lc.optimize(opt, fix_scale=False, max_env_blocks=env_blocks, stream=io.stream)
+        io.end()
+        nd = d.lc.update_normal_and_depth(stream=io.stream, tables={"mp_pos": o["pt_pos_opt"]})
+        io.end()
+    got = {k: io.down(p[k]) for k in ("conn", "n_conn", "corr_S", "kf_corr", "kf_Tcw_nc")}
+    got["propagate_status"] = io.down(p["status"])
+    got.update({k: io.down(d.d[k]) for k in ("kf_Tcw", "mp_pos", "normal", "max_distance", "min_distance",
+                                            "mp_corrected_by_kf", "mp_corrected_ref")})
+    got.update({k: io.down(a[k]) for k in ("kf_ids", "n_rows", "edge_v", "edge_kind", "n_edges", "pt_ref")})
+    got["assemble_status"] = io.down(a["status"])
+    got.update({k: io.down(o[k]) for k in ("kf_Tcw_opt", "pt_pos_opt", "Scw_opt", "trace", "chi2", "status")})
+    got["nd_status"] = io.down(nd)
+    got["env_blocks"] = env_blocks
+    got["dev"] = d                                    # the graph lives until the caller has synchronised
+    return got
+
+
+def test_run_chain_equals_the_model_up_to_the_assembly(model):
+    """The runner of the stream-order tests: its propagation and assembly against the model."""
+    from orbslam2commentedbyxcm_amd.optimizer import EssentialGraphOptimizer
+    opt = EssentialGraphOptimizer()
+    got = run_chain("hand", opt)
+    m = model["hand"]
+    asm = m["asm"]
+    nr = len(asm["kf_ids"])
+    assert int(got["n_rows"][0]) == nr and np.array_equal(got["kf_ids"][:nr], asm["kf_ids"])
+    ne = len(asm["edge_v"])
+    assert int(got["n_edges"][0]) == ne and np.array_equal(got["edge_v"][:ne], asm["edge_v"])
+    assert np.array_equal(got["edge_kind"][:ne], asm["edge_kind"]) and np.array_equal(got["pt_ref"], asm["pt_ref"])
+    assert got["trace"][0, 0] > 0
+    got["dev"].g.close()
+    opt.close()
 
 
 def close(got, want, spread):

@@ -69,6 +69,136 @@ class Map:
         self.g.close()
 
 
+RUN_KEYS = ("best", "best_n", "by_weight", "by_weight_n")
+
+
+def run_graph(g, tables, ids, io=None, decoy=None, N=10, w=15, erase=None, decoy_ids=None):
+    """refresh -> update_connections(ids) -> erase_keyframe -> the two getters, all on io's
+    stream with nothing read back in between.  io: a stream_order I/O object (default: blocking
+    uploads, a device synchronise around the calls); decoy: the tables that fill the inputs
+    before an ordered run's real uploads."""
+    import torch
+
+    import stream_order as SO
+    dev = torch.device("cuda", g.device)
+    io = io or SO.SyncIO(dev)
+    d = [io.up(a, b) for a, b in zip(tables, tables if decoy is None else decoy)]
+    K = g.max_keyframes
+    best, best_n = io.full((K, N), -9, torch.int32), io.full((K,), -9, torch.int32)
+    byw, byw_n = io.full((K, g.max_conn), -9, torch.int32), io.full((K,), -9, torch.int32)
+    io.begin()
+    g.refresh_observations(*d, stream=io.stream)
+    io.end()
+    h_ids = io.host(np.asarray(ids, np.int32), decoy_ids)
+    g.update_connections(h_ids, stream=io.stream)
+    io.end()
+    if erase is not None:
+        g.erase_keyframe(erase, stream=io.stream)
+        io.end()
+    g.best_covisibles(N, best, best_n, stream=io.stream)
+    io.end()
+    g.covisibles_by_weight(w, byw, byw_n, stream=io.stream)
+    io.end()
+    return dict(best=io.down(best), best_n=io.down(best_n), by_weight=io.down(byw), by_weight_n=io.down(byw_n))
+
+
+CHAIN_KEYS = ("poses", "mp_pos", "kf_mp", "kf_Tcw_opt", "pt_pos_opt", "erase", "level1", "n_erase", "trace", "status")
+
+
+def chain_decoy(sc):
+    """geometric_scene with the same map tables; poses, positions and keypoints moved."""
+    d = dict(sc)
+    d["poses"] = sc["poses"].copy()
+    d["poses"][:, [3, 7, 11]] += np.float32([0.02, -0.01, 0.015])
+    d["mp_pos"] = (sc["mp_pos"] + np.float32([0.03, 0.02, -0.04])).astype(np.float32)
+    d["xy"] = (sc["xy"] + np.float32([1.25, -0.75])).astype(np.float32)
+    d["u_right"] = np.where(sc["u_right"] >= 0, sc["u_right"] + np.float32(0.75), sc["u_right"]).astype(np.float32)
+    return d
+
+
+def chain_arrays(sc):
+    """The uploads of run_local_mapping."""
+    K, cap = sc["kf_mp"].shape
+    kps = keypoints(sc["xy"], sc["octave"]).view(np.uint8).reshape(K, cap, 28)
+    return dict(kf_mp=sc["kf_mp"], kf_n=sc["kf_n"], kf_bad=sc["kf_bad"], mp_bad=sc["mp_bad"], poses=sc["poses"],
+                mp_pos=sc["mp_pos"], kps=kps, u_right=sc["u_right"])
+
+
+def run_local_mapping(g, lba, sc, cur=5, io=None, decoy=None):
+    """LocalMapping's calls on one stream with nothing read back: refresh_observations ->
+    update_connections (all) -> local_ba_assemble -> LocalBundleAdjustment -> local_ba_apply.
+    io: a stream_order I/O object (default: blocking uploads, a device synchronise around the
+    calls); decoy: the scene whose arrays fill the inputs before an ordered run's real uploads."""
+    import torch
+
+    import stream_order as SO
+    dev = torch.device("cuda", g.device)
+    io = io or SO.SyncIO(dev)
+    A, Q = chain_arrays(sc), chain_arrays(sc if decoy is None else decoy)
+    d = {k: io.up(A[k], Q[k]) for k in A}
+    K, cap = sc["kf_mp"].shape
+    n_mp = len(sc["mp_bad"])
+    rows = {"B": (1,), "B1": (2,), "B3": (1, 3), "K": (K,), "K12": (K, 12), "P": (n_mp,), "P1": (n_mp + 1,),
+            "P3": (n_mp, 3), "O": (K * cap,)}
+    tables = {name: io.full(rows[shape], 0, getattr(torch, dtype)) for name, shape, dtype in lba.ASSEMBLY_TABLES}
+    out = {"kf_Tcw_opt": io.full((K, 12), float("nan"), torch.float32), "pt_pos_opt": io.full((n_mp, 3), float("nan"), torch.float32),
+           "erase": io.full((K * cap,), 9, torch.uint8), "level1": io.full((K * cap,), 9, torch.uint8),
+           "n_erase": io.full((1,), -9, torch.int32), "trace": io.full((1, 2, 2), -9, torch.int32),
+           "status": io.full((1,), -9, torch.int32)}
+    fx, fy, cx, cy, bf = sc["cam"]
+    io.begin()
+    g.refresh_observations(d["kf_mp"], d["kf_n"], d["kf_bad"], d["mp_bad"], stream=io.stream)
+    io.end()
+    g.update_connections(np.arange(K, dtype=np.int32), stream=io.stream)
+    io.end()
+    h_cur = io.host(np.asarray([cur], np.int32), np.asarray([cur + 1], np.int32))
+    lba.assemble_batch_device(g, h_cur, d["poses"], d["mp_pos"], K, n_mp, K * cap, tables=tables, stream=io.stream)
+    io.end()
+    sig = io.host(np.asarray(sc["inv_sigma2"], np.float32), np.asarray(sc["inv_sigma2"], np.float32)[::-1])
+    lba.local_ba_assembled_device(tables, d["kps"], d["u_right"], sig, fx, fy, cx, cy, bf, out=out, stream=io.stream)
+    io.end()
+    lba.apply_batch_device(g, tables, out["kf_Tcw_opt"], out["pt_pos_opt"], out["erase"], d["poses"], d["mp_pos"],
+                           d["kf_mp"], stream=io.stream)
+    io.end()
+    got = {k: io.down(v) for k, v in out.items()}
+    got.update(poses=io.down(d["poses"]), mp_pos=io.down(d["mp_pos"]), kf_mp=io.down(d["kf_mp"]))
+    return got
+
+
+def model_run(K, max_conn, tables, ids, N=10, w=15, erase=None):
+    """run_graph on the model."""
+    m = M.Graph(K, max_conn)
+    m.refresh_observations(*tables)
+    for k in sorted(ids):
+        m.update_connections(int(k))
+    if erase is not None:
+        m.erase_keyframe(erase)
+    best, byw = np.full((K, N), -1, np.int32), np.full((K, max_conn), -9, np.int32)
+    best_n, byw_n = np.zeros(K, np.int32), np.zeros(K, np.int32)
+    for k in range(K):
+        a, b = m.best_covisibles(k, N), m.covisibles_by_weight(k, w)
+        best[k, :len(a)], best_n[k] = a, len(a)
+        byw[k, :len(b)], byw_n[k] = b, len(b)
+    return dict(best=best, best_n=best_n, by_weight=byw, by_weight_n=byw_n)
+
+
+def test_run_graph_equals_model(torch_dev, lds_bound):
+    """The runner of the stream-order tests against the model."""
+    tables = M.scene(**M.GPU_SCENES["band24"])
+    K, cap = tables[0].shape
+    from orbslam2commentedbyxcm_amd import CovisibilityGraph
+    g = CovisibilityGraph(K, cap, len(tables[3]), 64)
+    got = run_graph(g, tables, list(range(K)), erase=7)
+    want = model_run(K, 64, tables, list(range(K)), erase=7)
+    assert np.array_equal(got["best"], want["best"]) and np.array_equal(got["best_n"], want["best_n"])
+    assert np.array_equal(got["by_weight_n"], want["by_weight_n"])
+    for k in range(K):
+        n = want["by_weight_n"][k]
+        assert np.array_equal(got["by_weight"][k, :n], want["by_weight"][k, :n])
+    assert want["best_n"].max() > 1 and want["by_weight_n"].max() > 1
+    g.close()
+
+
 @pytest.fixture(params=[None, 8], ids=["lds", "global"])
 def lds_bound(request, orbx_built):
     """K on both sides of the LDS-histogram bound: the bound lowered to 8 keyframes sends every

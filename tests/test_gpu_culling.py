@@ -42,7 +42,10 @@ def serial(request, orbx_built):
 class Scene:
     """A culling scene in HBM with the device graph, and the model graph over its own copy."""
 
-    def __init__(self, dev, m, max_conn=64):
+    def __init__(self, dev, m, max_conn=64, io=None, decoy=None):
+        """io: a stream_order I/O object for the float tables' uploads (default: blocking ones);
+        decoy: the scene (decoy_scene) whose tables are in place until an ordered run's real
+        uploads.  The integer map tables, which the graph is built from here, are the real ones."""
         import torch
 
         from orbslam2commentedbyxcm_amd import CovisibilityGraph, MapCuller
@@ -55,8 +58,9 @@ class Scene:
         keys = np.zeros((K, cap), L.KEYPOINT_DTYPE)
         keys["octave"] = m["octave"]
         self.d = {"kf_mp": t(m.get("kf_mp0", m["kf_mp"])), "kf_bad": t(m["kf_bad"]), "mp_bad": t(m["mp_bad"]),
-                  "kf_keys_un": t(keys.view(np.uint8).reshape(K, cap, 28)), "kf_u_right": t(m["u_right"]),
-                  "kf_depth": t(m["depth"]), "kf_th_depth": t(m["th_depth"]),
+                  "kf_keys_un": t(keys.view(np.uint8).reshape(K, cap, 28)),
+                  **{dk: t(m[mk]) if io is None else io.up(m[mk], (decoy or m)[mk])
+                     for dk, mk in (("kf_u_right", "u_right"), ("kf_depth", "depth"), ("kf_th_depth", "th_depth"))},
                   "kf_not_erase": None if m["not_erase"] is None else t(m["not_erase"]),
                   "kf_to_be_erased": t(m["to_be_erased"])}
         self.d_kf_n = t(m["kf_n"])
@@ -131,6 +135,121 @@ class Scene:
 
     def close(self):
         self.g.close()
+
+
+CULL_KEYS = ("cand", "cand_counts", "n_cand", "culled", "n_culled", "n_new_bad_mp", "status", "counts", "kf_mp", "kf_bad",
+             "mp_bad", "kf_to_be_erased")
+CULL_PAYLOAD = ("u_right", "depth", "th_depth")
+
+
+def decoy_scene(m):
+    """The culling scene with the same map and octaves; other stereo flags, depths and close-point
+    thresholds (any mixture is a valid scene: they only decide which points count)."""
+    d = dict(m)
+    d["u_right"] = np.where(m["u_right"] >= 0, np.float32(-1.0), np.float32(5.0)).astype(np.float32)
+    d["depth"] = (np.asarray(m["depth"], np.float32)[:, ::-1] * np.float32(3.0) + np.float32(0.5)).astype(np.float32)
+    d["th_depth"] = (np.asarray(m["th_depth"], np.float32) * np.float32(0.25) + np.float32(0.125)).astype(np.float32)
+    return d
+
+
+SET_BAD_IDS = (9, 0, 12)
+SET_BAD_DECOY_IDS = (10, 0, 13)            # in the caller's array once set_bad_flag has returned
+MAX_RECENT = 150
+
+
+def recent_inputs(m, max_conn=64):
+    """map_point_culling's tables for the scene and their decoy: the same length of list, other
+    valid ids in it, other found / visible counters and first keyframes."""
+    mm = C.copy_maps(m)
+    recent, found, visible, first = C.recent_case(mm, C.build_graph(mm, max_conn), 3, MAX_RECENT)
+    buf = np.full(MAX_RECENT, -7, np.int32)
+    buf[:len(recent)] = recent
+    real = dict(recent=buf, n=np.array([len(recent)], np.int32), first=np.asarray(first, np.int32),
+                found=np.asarray(found, np.int32), visible=np.asarray(visible, np.int32))
+    dbuf = buf.copy()
+    dbuf[:len(recent)] = np.asarray(recent)[::-1]
+    decoy = dict(recent=dbuf, n=real["n"], first=np.roll(real["first"], 7), found=real["visible"][::-1].copy(),
+                 visible=(real["found"][::-1] + 1).astype(np.int32))
+    return real, decoy
+
+
+def run_culling(dev, m, io=None, decoy=None, mode="keyframe"):
+    """On io's stream over a fresh graph (culling changes it), nothing read back in between:
+    mode "keyframe": covis_observation_counts_device -> keyframe_culling_device;
+    mode "set_bad": covis_set_bad_flag_device of SET_BAD_IDS (a host array);
+    mode "map_points": map_point_culling_device of recent_inputs(m).
+    io: a stream_order I/O object (default: blocking uploads, a device synchronise around the
+    calls); decoy: decoy_scene(m) (and recent_inputs' decoy) in place before the real uploads."""
+    import torch
+
+    import stream_order as SO
+    io = io or SO.SyncIO(dev)
+    sc = Scene(dev, m, io=io, decoy=decoy)
+    counts = io.full((len(m["mp_bad"]),), -9, torch.int32)
+    mono = m["monocular"]
+    extra = {}
+    if mode == "map_points":
+        real, other = recent_inputs(m)
+        r = {k: io.up(real[k], other[k] if decoy is not None else None) for k in real}
+    io.begin()
+    with io.on_stream():
+        if mode == "keyframe":
+            sc.cull.observation_counts(counts, stream=io.stream)
+            io.end()
+            t = sc.cull.keyframe_culling(m["cur"], mono, stream=io.stream)
+        elif mode == "set_bad":
+            ids = io.host(np.asarray(SET_BAD_IDS, np.int32), np.asarray(SET_BAD_DECOY_IDS, np.int32))
+            t = sc.cull.set_bad_flag(ids, stream=io.stream)
+        else:
+            n_culled = sc.cull.map_point_culling(10, mono, r["recent"], r["n"], r["first"], r["found"], r["visible"],
+                                                 stream=io.stream)
+            t = sc.cull._buffers()
+            extra = dict(recent=io.down(r["recent"]), n_recent=io.down(r["n"]), n_mp_culled=io.down(n_culled))
+        io.end()
+    got = {k: io.down(t[k]) for k in ("cand", "cand_counts", "n_cand", "culled", "n_culled", "n_new_bad_mp", "status")}
+    got.update(counts=io.down(counts), **{k: io.down(sc.d[k]) for k in ("kf_mp", "kf_bad", "mp_bad", "kf_to_be_erased")})
+    got.update(extra)
+    got["scene"] = sc                                 # the graph lives until the caller has synchronised
+    return got
+
+
+def test_run_culling_set_bad_and_map_points_equal_the_model(torch_dev):
+    """The other two modes of the stream-order tests' runner against the model."""
+    m = C.SCENES["band"]()
+    got = run_culling(torch_dev, m, mode="set_bad")
+    sc = got["scene"]
+    nb = st = 0
+    for k in SET_BAD_IDS:
+        _, s_, b_ = C.set_bad_flag(sc.mg, sc.m, int(k), m["not_erase"])
+        nb, st = nb + b_, st | s_
+    assert int(got["n_new_bad_mp"][0]) == nb and int(got["status"][0]) == st
+    sc.check_state()
+    sc.close()
+    got = run_culling(torch_dev, m, mode="map_points")
+    sc = got["scene"]
+    real, _ = recent_inputs(m)
+    n0 = int(real["n"][0])
+    kept, n = C.map_point_culling(sc.mg, sc.m, real["recent"][:n0], 10, m["monocular"], real["found"], real["visible"],
+                                  real["first"])
+    assert int(got["n_recent"][0]) == len(kept) and got["recent"][:len(kept)].tolist() == list(kept)
+    assert int(got["n_mp_culled"][0]) == n
+    sc.check_state()
+    sc.close()
+
+
+def test_run_culling_equals_the_model(torch_dev):
+    """The runner of the stream-order tests against the model."""
+    m = C.SCENES["band"]()
+    got = run_culling(torch_dev, m)
+    sc = got["scene"]
+    want = C.key_frame_culling(sc.mg, sc.m, m["cur"], m["monocular"], m["not_erase"])
+    n = len(want["cand"])
+    assert int(got["n_cand"][0]) == n and got["cand"][:n].tolist() == want["cand"].tolist()
+    assert got["cand_counts"][:n].tolist() == want["cand_counts"].tolist()
+    assert got["culled"][:len(want["culled"])].tolist() == want["culled"].tolist() and len(want["culled"]) > 0
+    assert int(got["n_new_bad_mp"][0]) == want["n_new_bad_mp"] and int(got["status"][0]) == want["status"]
+    sc.check_state()
+    sc.close()
 
 
 @pytest.mark.parametrize("name", list(C.SCENES))

@@ -87,35 +87,44 @@ def blocks_of(sc, dense=False):
     return M.envelope(len(sc["Tcw"]), sc["loop"], sc["edge_v"], dense)[2]
 
 
-def run_batch(opt, scenes, iterations=0, dense=False, max_env_blocks=None, optional=True):
+def run_batch(opt, scenes, iterations=0, dense=False, max_env_blocks=None, optional=True, io=None, decoy=None):
+    """io: a stream_order I/O object (default: blocking uploads, a device synchronise around the
+    call); decoy: the scenes whose arrays fill the inputs before an ordered run's real uploads.
+    The per-problem rows are views that an ordered run fills when its stream is synchronised."""
     import torch
+
+    import stream_order as SO
     P = M.pack(scenes)
+    Q = P if decoy is None else M.pack(decoy)
     B = len(scenes)
     dev = torch.device("cuda", opt.device)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    io = io or SO.SyncIO(dev)
     nk, npt = len(P["Tcw"]), len(P["pos"])
-    d_T = torch.full((nk, 12), float("nan"), dtype=torch.float32, device=dev)
-    d_X = torch.full((npt, 3), float("nan"), dtype=torch.float32, device=dev)
-    d_st = torch.full((B,), -9, dtype=torch.int32, device=dev)
-    d_S = torch.full((nk, 8), float("nan"), dtype=torch.float64, device=dev) if optional else None
-    d_tr = torch.full((B, 2), -9, dtype=torch.int32, device=dev) if optional else None
-    d_chi = torch.full((B, 2), float("nan"), dtype=torch.float64, device=dev) if optional else None
+    d_T = io.full((nk, 12), float("nan"), torch.float32)
+    d_X = io.full((npt, 3), float("nan"), torch.float32)
+    d_st = io.full((B,), -9, torch.int32)
+    d_S = io.full((nk, 8), float("nan"), torch.float64) if optional else None
+    d_tr = io.full((B, 2), -9, torch.int32) if optional else None
+    d_chi = io.full((B, 2), float("nan"), torch.float64) if optional else None
     if max_env_blocks is None:
         max_env_blocks = max(blocks_of(sc, dense) for sc in scenes)
-    torch.cuda.synchronize(dev)
+    ins = [io.up(P[k], Q[k]) for k in ("kf_off", "Tcw", "corr", "corr_S", "loop", "edge_off", "edge_v", "edge_kind",
+                                       "pt_off", "pos", "pt_ref")]
+    io.begin()
     opt.essential_graph_batch_device(
-        t(P["kf_off"]), t(P["Tcw"]), t(P["corr"]), t(P["corr_S"]), t(P["loop"]), t(P["edge_off"]), t(P["edge_v"]),
-        t(P["edge_kind"]), t(P["pt_off"]), t(P["pos"]), t(P["pt_ref"]), bool(scenes[0]["fix_scale"]), max_env_blocks,
+        *ins, bool(scenes[0]["fix_scale"]), max_env_blocks,
         d_T, d_X, d_st, d_Scw_opt=d_S, d_trace=d_tr, d_chi2=d_chi, iterations=iterations, dense=dense,
-        stream=torch.cuda.current_stream(dev))
-    torch.cuda.synchronize(dev)
-    cpu = lambda x: None if x is None else x.cpu().numpy()  # noqa: E731
-    T, X, S = cpu(d_T), cpu(d_X), cpu(d_S)
+        stream=io.stream)
+    io.end()
+    T, X, S, st, tr, chi = (io.down(x) for x in (d_T, d_X, d_S, d_st, d_tr, d_chi))
     out = []
     for b in range(B):
         k0, k1, p0, p1 = P["kf_off"][b], P["kf_off"][b + 1], P["pt_off"][b], P["pt_off"][b + 1]
-        out.append(dict(Tcw=T[k0:k1], pos=X[p0:p1], Scw=None if S is None else S[k0:k1], status=int(cpu(d_st)[b]),
-                        trace=None if d_tr is None else cpu(d_tr)[b], chi2=None if d_chi is None else cpu(d_chi)[b]))
+        out.append(dict(Tcw=T[k0:k1], pos=X[p0:p1], Scw=None if S is None else S[k0:k1], status=st[b:b + 1],
+                        trace=None if tr is None else tr[b], chi2=None if chi is None else chi[b]))
+    if not io.ordered:
+        for o in out:
+            o["status"] = int(o["status"][0])
     return out
 
 

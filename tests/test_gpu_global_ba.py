@@ -57,34 +57,46 @@ def keypoints(xy, octv):
     return k
 
 
-def run_batch(opt, scenes, iterations, robust, max_env_blocks=None, dense=False, trace=True, chi2=True):
-    import torch
+def upload_arrays(scenes):
+    """The arrays of a batch as they are uploaded (kps: the 28-byte keypoint records)."""
     A = G.batch_arrays(scenes)
+    A["kps"] = keypoints(A["kps_xy"], A["kps_oct"]).view(np.uint8).reshape(A["n_slots"], A["cap"], 28)
+    return A
+
+
+def run_batch(opt, scenes, iterations, robust, max_env_blocks=None, dense=False, trace=True, chi2=True, io=None,
+              decoy=None):
+    """io: a stream_order I/O object (default: blocking uploads, a device synchronise around the
+    call); decoy: the scenes whose arrays fill the inputs before an ordered run's real uploads."""
+    import torch
+
+    import stream_order as SO
+    A = upload_arrays(scenes)
+    Q = A if decoy is None else upload_arrays(decoy)
     B = len(scenes)
     if max_env_blocks is None:
         max_env_blocks = max(G.envelope_blocks(s, dense) for s in scenes)
     dev = torch.device("cuda", opt.device)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    io = io or SO.SyncIO(dev)
     n_kf, n_pt = len(A["fixed"]), len(A["pos"])
-    kps = keypoints(A["kps_xy"], A["kps_oct"])
-    d_T = torch.full((n_kf, 12), float("nan"), dtype=torch.float32, device=dev)
-    d_X = torch.full((n_pt, 3), float("nan"), dtype=torch.float32, device=dev)
-    d_in = torch.full((n_pt,), 9, dtype=torch.uint8, device=dev)
-    d_st = torch.full((B,), -9, dtype=torch.int32, device=dev)
-    d_tr = torch.full((B, 2), -9, dtype=torch.int32, device=dev) if trace else None
-    d_c2 = torch.full((B, 2), float("nan"), dtype=torch.float64, device=dev) if chi2 else None
+    d_T = io.full((n_kf, 12), float("nan"), torch.float32)
+    d_X = io.full((n_pt, 3), float("nan"), torch.float32)
+    d_in = io.full((n_pt,), 9, torch.uint8)
+    d_st = io.full((B,), -9, torch.int32)
+    d_tr = io.full((B, 2), -9, torch.int32) if trace else None
+    d_c2 = io.full((B, 2), float("nan"), torch.float64) if chi2 else None
     s0 = scenes[0]
     fx, fy, cx, cy, bf = s0["cam"]
-    torch.cuda.synchronize(dev)
+    ins = [io.up(A[k], Q[k]) for k in ("kf_off", "Tcw", "fixed", "slot", "pt_off", "pos", "obs_off", "obs_kf", "obs_kp",
+                                       "kps", "u_right")]
+    sig = io.host(np.asarray(s0["inv_sigma2"], np.float32), np.asarray(s0["inv_sigma2"], np.float32)[::-1])
+    io.begin()
     opt.global_ba_batch_device(
-        t(A["kf_off"]), t(A["Tcw"]), t(A["fixed"]), t(A["slot"]), t(A["pt_off"]), t(A["pos"]), t(A["obs_off"]),
-        t(A["obs_kf"]), t(A["obs_kp"]), t(kps.view(np.uint8).reshape(A["n_slots"], A["cap"] * 28)).view(A["n_slots"], A["cap"], 28),
-        t(A["u_right"]), s0["inv_sigma2"], fx, fy, cx, cy, bf, iterations, robust, max_env_blocks, d_T, d_X, d_in, d_st,
-        d_trace=d_tr, d_chi2=d_c2, dense=dense, stream=torch.cuda.current_stream(dev))
-    torch.cuda.synchronize(dev)
-    cpu = lambda x: None if x is None else x.cpu().numpy()  # noqa: E731
-    return dict(Tcw=cpu(d_T), pos=cpu(d_X), pt_included=cpu(d_in), status=cpu(d_st), trace=cpu(d_tr), chi2=cpu(d_c2),
-                arrays=A)
+        *ins, sig, fx, fy, cx, cy, bf, iterations, robust, max_env_blocks, d_T, d_X, d_in, d_st,
+        d_trace=d_tr, d_chi2=d_c2, dense=dense, stream=io.stream)
+    io.end()
+    return dict(Tcw=io.down(d_T), pos=io.down(d_X), pt_included=io.down(d_in), status=io.down(d_st), trace=io.down(d_tr),
+                chi2=io.down(d_c2), arrays=A)
 
 
 def part(got, b):

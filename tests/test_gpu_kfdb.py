@@ -59,6 +59,107 @@ def _apply(db, ops):
     flush()
 
 
+def bow_tables(bows):
+    """Host BowVectors in the transform_batch_device layout: words, values, counts."""
+    from orbslam2commentedbyxcm_amd.database import bow_arrays
+    arrs = [bow_arrays(b) for b in bows]
+    cap = max([len(w) for w, _ in arrs] + [1])
+    W, V, N = np.zeros((len(arrs), cap), np.int32), np.zeros((len(arrs), cap), np.float64), np.zeros(len(arrs), np.int32)
+    for i, (w, v) in enumerate(arrs):
+        W[i, :len(w)], V[i, :len(w)], N[i] = w, v, len(w)
+    return dict(word=W, value=V, n=N)
+
+
+def run_add(db, ids, bows, io=None, decoy=None, decoy_ids=None):
+    """kfdb_add_batch_device of host BowVectors through io (a stream_order I/O object; default:
+    blocking uploads, a device synchronise around the call)."""
+    import torch
+
+    import stream_order as SO
+    io = io or SO.SyncIO(torch.device("cuda", db.device))
+    T, Q = bow_tables(bows), bow_tables(bows if decoy is None else decoy)
+    d = {k: io.up(T[k], Q[k]) for k in T}
+    h_ids = io.host(np.asarray(ids, np.int32), decoy_ids)
+    io.begin()
+    db.add_batch_device(h_ids, d["word"], d["value"], d["n"], T["word"].shape[1], stream=io.stream_ptr)
+    io.end()
+
+
+LOOP_CONNECTED = ([3, 7, 11], [])          # GetConnectedKeyFrames() of the two loop queries
+LOOP_MIN_SCORE = (0.01, 0.0)
+DECOY_MIN_SCORE = (0.4, 0.3)              # in place of LOOP_MIN_SCORE until an ordered run's real upload
+QUERY_KEYS = ("score", "cand", "ncand", "loop_cand", "loop_ncand")
+
+
+def run_queries(db, query, score_ids, reloc_queries, io=None, decoy=None, max_cand=32, min_score=LOOP_MIN_SCORE,
+                switch_io=None):
+    """kfdb_score_device of one query against score_ids, then one batched
+    DetectRelocalizationCandidates and one batched DetectLoopCandidates of reloc_queries, on io's
+    stream with nothing read back in between.  decoy = (query, reloc_queries) with the same words.
+    switch_io: the I/O object whose stream the calls after the score go to (the stream switch)."""
+    import torch
+
+    import stream_order as SO
+    io = io or SO.SyncIO(torch.device("cuda", db.device))
+    dq, dr = (query, reloc_queries) if decoy is None else decoy
+    T, Q = bow_tables([query]), bow_tables([dq])
+    R, RQ = bow_tables(reloc_queries), bow_tables(dr)
+    q = {k: io.up(T[k], Q[k]) for k in T}
+    r = {k: io.up(R[k], RQ[k]) for k in R}
+    d_ids = io.up(np.asarray(score_ids, np.int32))
+    d_score = io.full((len(score_ids),), -7.0, torch.float32)
+    B = len(reloc_queries)
+    conn_off = np.concatenate([[0], np.cumsum([len(c) for c in LOOP_CONNECTED[:B]])]).astype(np.int32)
+    conn_ids = np.asarray([i for c in LOOP_CONNECTED[:B] for i in c] + [0], np.int32)
+    d_coff, d_cids = io.up(conn_off), io.up(conn_ids)
+    d_min = io.up(np.asarray(min_score[:B], np.float32), None if decoy is None else np.asarray(DECOY_MIN_SCORE[:B], np.float32))
+    out = {"cand": io.full((B, max_cand), -1, torch.int32), "ncand": io.full((B,), -9, torch.int32), "words": None,
+           "score": None}
+    loop = {"cand": io.full((B, max_cand), -1, torch.int32), "ncand": io.full((B,), -9, torch.int32), "words": None,
+            "score": None}
+    io.begin()
+    db.score_device(q["word"], q["value"], q["n"], T["word"].shape[1], d_ids, d_score, stream=io.stream_ptr)
+    io.end()
+    io2 = switch_io or io
+    db.detect_relocalization_candidates_device(r["word"], r["value"], r["n"], R["word"].shape[1], out,
+                                               stream=io2.stream_ptr)
+    if switch_io is None:
+        io.end()
+    else:
+        switch_io.first_stream_done = io.stream.query()      # read as soon as the switched call returns
+    db.detect_loop_candidates_device(r["word"], r["value"], r["n"], R["word"].shape[1], d_coff, d_cids, d_min, loop,
+                                     stream=io2.stream_ptr)
+    if switch_io is None:
+        io.end()
+    return dict(score=io.down(d_score), cand=io2.down(out["cand"]), ncand=io2.down(out["ncand"]),
+                loop_cand=io2.down(loop["cand"]), loop_ncand=io2.down(loop["ncand"]))
+
+
+def test_device_runners_equal_model(voc):
+    """The runners of the stream-order tests against the model: add + score at n = 65 and one
+    batched relocalisation detection."""
+    rng = np.random.default_rng(165)
+    n = 65
+    bows = [M.random_bow(rng, int(rng.integers(1, 301))) for _ in range(n)]
+    model, db = M.Database(), _db(voc, n)
+    for i, b in enumerate(bows):
+        model.add(i, b)
+    run_add(db, list(range(n)), bows)
+    ids = [int(i) for i in rng.permutation(n)]
+    q = M.random_bow(rng, 150)
+    rq = [M.perturbed(rng, bows[7], 0.7, 20), M.random_bow(rng, 200)]
+    got = run_queries(db, q, ids, rq, max_cand=n)
+    assert np.array_equal(_u32(got["score"]), _u32(model.score(q, ids)))
+    for b, x in enumerate(rq):
+        want = model.detect_relocalization_candidates(x)
+        assert got["cand"][b, :got["ncand"][b]].tolist() == want, b
+    assert got["ncand"].max() > 0
+    for b, x in enumerate(rq):
+        want = model.detect_loop_candidates(x, set(LOOP_CONNECTED[b]), LOOP_MIN_SCORE[b])
+        assert got["loop_cand"][b, :got["loop_ncand"][b]].tolist() == want, ("loop", b)
+    db.close()
+
+
 def _u32(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 

@@ -59,33 +59,45 @@ def keypoints(xy, octv):
     return k
 
 
-def run_batch(opt, scenes, level1=True, trace=True, max_free_kf=0):
-    import torch
+def upload_arrays(scenes):
+    """The arrays of a batch as they are uploaded (kps: the 28-byte keypoint records)."""
     A = M.batch_arrays(scenes)
+    A["kps"] = keypoints(A["kps_xy"], A["kps_oct"]).view(np.uint8).reshape(A["n_slots"], A["cap"], 28)
+    return A
+
+
+def run_batch(opt, scenes, level1=True, trace=True, max_free_kf=0, io=None, decoy=None):
+    """io: a stream_order I/O object (default: blocking uploads, a device synchronise around the
+    call); decoy: the scenes whose arrays fill the inputs before an ordered run's real uploads."""
+    import torch
+
+    import stream_order as SO
+    A = upload_arrays(scenes)
+    Q = A if decoy is None else upload_arrays(decoy)
     B = len(scenes)
     dev = torch.device("cuda", opt.device)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    io = io or SO.SyncIO(dev)
+    t = lambda k: io.up(A[k], Q[k])  # noqa: E731
     n_kf, n_pt, n_obs = len(A["fixed"]), len(A["pos"]), len(A["obs_kf"])
-    kps = keypoints(A["kps_xy"], A["kps_oct"])
-    d_T = torch.full((n_kf, 12), float("nan"), dtype=torch.float32, device=dev)
-    d_X = torch.full((n_pt, 3), float("nan"), dtype=torch.float32, device=dev)
-    d_er = torch.full((n_obs,), 9, dtype=torch.uint8, device=dev)
-    d_l1 = torch.full((n_obs,), 9, dtype=torch.uint8, device=dev) if level1 else None
-    d_ne = torch.full((B,), -9, dtype=torch.int32, device=dev)
-    d_st = torch.full((B,), -9, dtype=torch.int32, device=dev)
-    d_tr = torch.full((B, 2, 2), -9, dtype=torch.int32, device=dev) if trace else None
+    d_T = io.full((n_kf, 12), float("nan"), torch.float32)
+    d_X = io.full((n_pt, 3), float("nan"), torch.float32)
+    d_er = io.full((n_obs,), 9, torch.uint8)
+    d_l1 = io.full((n_obs,), 9, torch.uint8) if level1 else None
+    d_ne = io.full((B,), -9, torch.int32)
+    d_st = io.full((B,), -9, torch.int32)
+    d_tr = io.full((B, 2, 2), -9, torch.int32) if trace else None
     s0 = scenes[0]
     fx, fy, cx, cy, bf = s0["cam"]
-    torch.cuda.synchronize(dev)
+    ins = [t(k) for k in ("kf_off", "Tcw", "fixed", "slot", "pt_off", "pos", "obs_off", "obs_kf", "obs_kp", "kps",
+                          "u_right")]
+    sig = io.host(np.asarray(s0["inv_sigma2"], np.float32), np.asarray(s0["inv_sigma2"], np.float32)[::-1])
+    io.begin()
     opt.local_ba_batch_device(
-        t(A["kf_off"]), t(A["Tcw"]), t(A["fixed"]), t(A["slot"]), t(A["pt_off"]), t(A["pos"]), t(A["obs_off"]),
-        t(A["obs_kf"]), t(A["obs_kp"]), t(kps.view(np.uint8).reshape(A["n_slots"], A["cap"] * 28)).view(A["n_slots"], A["cap"], 28),
-        t(A["u_right"]), s0["inv_sigma2"], fx, fy, cx, cy, bf, d_T, d_X, d_er, d_ne, d_st, d_level1=d_l1, d_trace=d_tr,
-        max_free_kf=max_free_kf, stream=torch.cuda.current_stream(dev))
-    torch.cuda.synchronize(dev)
-    cpu = lambda x: None if x is None else x.cpu().numpy()  # noqa: E731
-    return dict(Tcw=cpu(d_T), pos=cpu(d_X), erase=cpu(d_er), level1=cpu(d_l1), n_erase=cpu(d_ne), status=cpu(d_st),
-                trace=cpu(d_tr), arrays=A)
+        *ins, sig, fx, fy, cx, cy, bf, d_T, d_X, d_er, d_ne, d_st, d_level1=d_l1, d_trace=d_tr,
+        max_free_kf=max_free_kf, stream=io.stream)
+    io.end()
+    return dict(Tcw=io.down(d_T), pos=io.down(d_X), erase=io.down(d_er), level1=io.down(d_l1), n_erase=io.down(d_ne),
+                status=io.down(d_st), trace=io.down(d_tr), arrays=A)
 
 
 def part(got, b):

@@ -88,6 +88,79 @@ class Scene:
         self.g.close()
 
 
+TRACK_KEYS = ("local_kf", "local_kf_n", "ref_kf", "local_off", "local_ids", "counts", "status", "frame_mp", "inliers",
+              "ok", "found")
+TRACK_OUT_ONLY = ("local_off", "counts", "status", "inliers", "ok")     # the others are inputs as well
+
+
+def track_inputs(sc, seed=0):
+    """frame_mp / n of the scene's case and the tally's flags, counts and found counters."""
+    c = sc.c if hasattr(sc, "c") else sc
+    rng = np.random.default_rng(seed)
+    fm = np.asarray(c["frame_mp"], np.int32)
+    n_mp = len(c["map"][3])
+    B = len(fm)
+    return dict(frame_mp=fm, n=np.asarray(c["n"], np.int32), outlier=(rng.random(fm.shape) < 0.2).astype(np.uint8),
+                observations=rng.integers(0, 3, n_mp).astype(np.int32), rec=(np.arange(B) % 2).astype(np.uint8),
+                found=rng.integers(0, 9, n_mp).astype(np.int32))
+
+
+def track_decoy(inp):
+    """Another valid set of the same id range: the frames' tables dealt to other frames, other
+    flags and counters; the counts are the real ones."""
+    rng = np.random.default_rng(91)
+    return dict(frame_mp=np.roll(inp["frame_mp"], 1, axis=0)[:, ::-1].copy(), n=inp["n"],
+                outlier=(rng.random(inp["outlier"].shape) < 0.4).astype(np.uint8),
+                observations=rng.integers(0, 3, len(inp["observations"])).astype(np.int32), rec=inp["rec"],
+                found=rng.integers(0, 9, len(inp["found"])).astype(np.int32))
+
+
+def run_track(sc, inp, io=None, decoy=None):
+    """update_local_map -> tally on io's stream with nothing read back in between; the in/out
+    lists start empty.  io: a stream_order I/O object (default: blocking uploads, a device
+    synchronise around the calls); decoy: the inputs that are in place before an ordered run's
+    real uploads."""
+    import stream_order as SO
+    io = io or SO.SyncIO(sc.dev)
+    Q = inp if decoy is None else decoy
+    mk = sc.c["max_local_kf"]
+    B = len(inp["frame_mp"])
+    lists = LM.initial_lists(B, mk)
+    want = LM.update_local_map_batch(sc.m, inp["frame_mp"], inp["n"], *lists, mk, BIG, BIG)
+    total = int(want["local_off"][-1]) + 7
+    d = {k: io.up(inp[k], Q[k]) for k in inp}
+    buf = sc.trk.buffers(B, mk, total)
+    for name, a in zip(("local_kf", "local_kf_n", "ref_kf"), lists):
+        io.put(buf[name], np.asarray(a, np.int32))
+    io.put(buf["local_ids"], np.full(total, -5, np.int32))
+    io.begin()
+    with io.on_stream():
+        sc.trk.update_local_map(d["frame_mp"], d["n"], mk, BIG, total, stream=io.stream)
+        io.end()
+        inl, ok = sc.trk.tally(d["frame_mp"], d["n"], d["outlier"], d["observations"], False, True, d["rec"], d["found"],
+                               stream=io.stream)
+        io.end()
+    got = {k: io.down(buf[k]) for k in ("local_kf", "local_kf_n", "ref_kf", "local_off", "local_ids", "counts", "status")}
+    got.update(frame_mp=io.down(d["frame_mp"]), inliers=io.down(inl), ok=io.down(ok), found=io.down(d["found"]), want=want)
+    return got
+
+
+def test_run_track_equals_the_model(torch_dev, lds_bound):
+    """The runner of the stream-order tests against the model."""
+    name = LM.GPU_CASES[0]
+    sc = Scene(torch_dev, name)
+    inp = track_inputs(sc)
+    got = run_track(sc, inp)
+    want = got["want"]
+    LM.assert_same({k: got[k] for k in ("local_kf", "local_kf_n", "ref_kf", "local_off", "local_ids", "counts", "status")},
+                   want)
+    w_fm, w_inl, w_ok, w_found = LM.tally(want["frame_mp"], inp["n"], inp["outlier"], inp["observations"], False, True,
+                                          inp["rec"], inp["found"])
+    assert np.array_equal(got["frame_mp"], w_fm) and np.array_equal(got["inliers"], w_inl)
+    assert np.array_equal(got["ok"], w_ok) and np.array_equal(got["found"], w_found)
+    sc.close()
+
+
 @pytest.mark.parametrize("name", LM.GPU_CASES)
 def test_batch_and_single_frames_equal_the_model(torch_dev, lds_bound, name):
     sc = Scene(torch_dev, name)
@@ -215,6 +288,181 @@ def test_tally_equals_the_model(torch_dev):
         seen |= set(zip(w_ok.tolist(), rec.tolist()))
     assert seen == {(0, 0), (1, 0), (0, 1), (1, 1)}
     g.close()
+
+
+# ---- the TrackLocalMap chain of INTEGRATION.md as a runner (tests/test_gpu_stream_order.py) -----------
+TLM_TABLE = ("pos", "desc", "normal", "max_distance", "min_distance", "observations", "bad")
+TLM_PAYLOAD = {"pos", "desc", "normal", "max_distance", "min_distance", "observations", "kps", "kp_desc", "T"}
+TLM_KEYS = ("local_kf", "local_kf_n", "ref_kf", "local_off", "local_ids", "counts", "status", "frame_mp", "nmatches",
+            "Tcw_opt", "outlier", "ninliers", "ninit", "inliers", "ok", "found")
+TLM_OUT_ONLY = ("local_off", "counts", "status", "nmatches", "Tcw_opt", "ninliers", "ninit", "inliers", "ok")
+TLM_INV_SIGMA2 = (1.2 ** (-2.0 * np.arange(8))).astype(np.float32)
+
+
+def tlm_setup(B=6):
+    """The scene of test_chain_update_local_map_search_local_points_tally: a posed sequence whose
+    frames are also the keyframes, the graph over it, the model's UpdateLocalMap, and the host
+    arrays of every device input."""
+    import torch
+
+    import covisibility_model as M
+    from orbslam2commentedbyxcm_amd import CovisibilityGraph, LocalMapTracker, ORBmatcher
+    from orbslam2commentedbyxcm_amd import _lib as L
+    from orbslam2commentedbyxcm_amd.optimizer import PoseOptimizer
+    from test_gpu_posed import _mappoint_table, _sequence_on_gpu
+    seq = _sequence_on_gpu(types.SimpleNamespace(KEYPOINT_DTYPE=L.KEYPOINT_DTYPE), B, 30)
+    cap, n, dev = seq["cap"], seq["n"], seq["dev"]
+    tab = _mappoint_table(seq, 31)
+    rng = np.random.default_rng(33)
+    kf_mp = np.full((B, cap), -1, np.int32)
+    for f in range(B):
+        kf_mp[f, :n[f]] = f * cap + np.arange(n[f])
+        if f > 0:
+            sel = np.flatnonzero(rng.random(n[f]) < 0.2)[:n[f - 1]]
+            kf_mp[f, sel] = (f - 1) * cap + rng.permutation(n[f - 1])[:len(sel)]
+    kf_bad = np.zeros(B, np.uint8)
+    mg = M.Graph(B, 16)
+    mg.refresh_observations(kf_mp, n, kf_bad, tab["bad"])
+    for k in range(B):
+        mg.update_connections(k)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    g = CovisibilityGraph(B, cap, B * cap, 16)
+    d_map = (t(kf_mp), t(n.astype(np.int32)), t(kf_bad), t(tab["bad"]))
+    torch.cuda.synchronize()
+    g.refresh_observations(*d_map)
+    g.update_connections(list(range(B)))
+    torch.cuda.synchronize()
+    fmp0 = np.full((B, cap), -1, np.int32)
+    for b in range(B):
+        nb = [f for f in (b - 1, b + 1) if 0 <= f < B]
+        pool = np.concatenate([f * cap + np.arange(n[f]) for f in nb])
+        sel = np.flatnonzero(rng.random(n[b]) < 0.25)
+        fmp0[b, sel] = rng.choice(pool, len(sel), replace=False)
+    mk, max_points = 16, B * cap
+    want = LM.update_local_map_batch(mg, fmp0, n, *LM.initial_lists(B, mk), mk, max_points, BIG)
+    m = ORBmatcher(0.8, False)
+    inp = dict({k: tab[k] for k in TLM_TABLE}, kps=seq["d_kps"].cpu().numpy(), kp_desc=seq["desc"],
+               n=n.astype(np.int32), T=np.asarray(seq["T"], np.float32), fmp0=fmp0,
+               rec=np.array([0, 1] * (B // 2), np.uint8), found=np.zeros(B * cap, np.int32))
+    return dict(seq=seq, dev=dev, B=B, cap=cap, g=g, d_map=d_map, m=m, pose=PoseOptimizer(matcher=m), trk=LocalMapTracker(g),
+                mk=mk, max_points=max_points, max_total=int(want["local_off"][-1]) + 11, want=want, inp=inp,
+                sf=np.asarray(seq["ex"].GetScaleFactors(), np.float32))
+
+
+def tlm_decoy(inp):
+    """The inputs with the same ids, counts and octaves; positions, descriptors, normals,
+    distances, Observations(), keypoint coordinates and poses are others."""
+    d = dict(inp)
+    d["pos"] = (inp["pos"] + np.float32([0.05, -0.03, 0.04])).astype(np.float32)
+    d["desc"] = inp["desc"] ^ np.uint8(0x5A)
+    d["kp_desc"] = inp["kp_desc"] ^ np.uint8(0x33)
+    d["normal"] = np.ascontiguousarray(inp["normal"][:, ::-1])
+    d["max_distance"] = (inp["max_distance"] * np.float32(1.5)).astype(np.float32)
+    d["min_distance"] = (inp["min_distance"] * np.float32(0.5)).astype(np.float32)
+    d["observations"] = ((inp["observations"] + 1) % 4).astype(np.int32)
+    kps = inp["kps"].copy()
+    xy = kps[..., :2].view(np.float32)
+    xy += np.float32(2.5)
+    d["kps"] = kps
+    d["T"] = inp["T"].copy()
+    d["T"][:, [3, 7, 11]] += np.float32([0.02, -0.01, 0.03])
+    return d
+
+
+def tlm_decoy_offsets(off):
+    """Another valid partition of the same list: the inner boundaries halved."""
+    o = np.array(off, np.int32, copy=True)
+    o[1:-1] = o[1:-1] // 2
+    return o
+
+
+def run_track_chain(st, io=None, decoy=None, inp=None, host_offsets=False):
+    """UpdateLocalMap -> SearchLocalPoints from the device offsets -> PoseOptimization -> tally on
+    io's stream with nothing read back; the in/out lists start empty.  host_offsets: instead, the
+    host-offset search_local_points_device alone on the model's lists (the yardstick of the chain
+    test), its host offsets and scale factors given through io.host.  io: a stream_order I/O
+    object (default: blocking uploads, a device synchronise around the calls); decoy: tlm_decoy's
+    arrays, in place before an ordered run's real uploads."""
+    import torch
+
+    import match_scenes as S
+    import stream_order as SO
+    io = io or SO.SyncIO(st["dev"])
+    inp = st["inp"] if inp is None else inp
+    Q = inp if decoy is None else decoy
+    B, cap, mk, want = st["B"], st["cap"], st["mk"], st["want"]
+    d = {k: io.up(inp[k], Q[k]) for k in inp if k != "fmp0"}
+    d_tab = {k: d[k] for k in TLM_TABLE}
+    d_fmp = io.up(want["frame_mp"] if host_offsets else inp["fmp0"])
+    d_nm = io.full((B,), -7, torch.int32)
+    cam = (S.FX, S.FY, S.CX, S.CY)
+    if host_offsets:
+        sf = io.host(st["sf"], st["sf"][::-1].copy())
+        d_ids = io.up(want["local_ids"])
+        off = io.host(np.asarray(want["local_off"], np.int32), tlm_decoy_offsets(want["local_off"]))
+        io.begin()
+        st["m"].search_local_points_device(d_tab, d["kps"], d["kp_desc"], d["n"], d["T"], off, d_ids, d_fmp, d_nm, sf, *cam,
+                                           640, 480, stream=io.stream)
+        io.end()
+        return dict(frame_mp=io.down(d_fmp), nmatches=io.down(d_nm))
+    buf = st["trk"].buffers(B, mk, st["max_total"])
+    for name, a in zip(("local_kf", "local_kf_n", "ref_kf"), LM.initial_lists(B, mk)):
+        io.put(buf[name], np.asarray(a, np.int32))
+    io.put(buf["local_ids"], np.full(st["max_total"], -5, np.int32))
+    d_Tout = io.full((B, 12), float("nan"), torch.float32)
+    d_outl = io.full((B, cap), 0, torch.uint8)
+    d_ninl, d_nini = io.full((B,), -9, torch.int32), io.full((B,), -9, torch.int32)
+    io.begin()
+    with io.on_stream():
+        lm = st["trk"].update_local_map(d_fmp, d["n"], mk, st["max_points"], st["max_total"], stream=io.stream)
+        io.end()
+        sf = io.host(st["sf"], st["sf"][::-1].copy())          # a host table is given just before its call:
+        st["m"].search_local_points_offsets_device(d_tab, d["kps"], d["kp_desc"], d["n"], d["T"], lm["local_off"],
+                                                   lm["local_ids"], d_fmp, d_nm, sf, *cam, 640, 480,
+                                                   max_local_points=st["max_points"], max_total=st["max_total"],
+                                                   stream=io.stream)
+        io.end()                                               # io.end() overwrites it with its decoy
+        sig = io.host(TLM_INV_SIGMA2, TLM_INV_SIGMA2[::-1].copy())
+        st["pose"].pose_optimization_batch_device(d["kps"], d["n"], d_fmp, d["pos"], sig, *cam, 0.0, d["T"], d_Tout, d_outl,
+                                                  d_ninl, d_nini, stream=io.stream)
+        io.end()
+        inl, ok = st["trk"].tally(d_fmp, d["n"], d_outl, d["observations"], False, False, d["rec"], d["found"],
+                                  stream=io.stream)
+        io.end()
+    got = {k: io.down(buf[k]) for k in ("local_kf", "local_kf_n", "ref_kf", "local_off", "local_ids", "counts", "status")}
+    got.update(frame_mp=io.down(d_fmp), nmatches=io.down(d_nm), Tcw_opt=io.down(d_Tout), outlier=io.down(d_outl),
+               ninliers=io.down(d_ninl), ninit=io.down(d_nini), inliers=io.down(inl), ok=io.down(ok), found=io.down(d["found"]))
+    return got
+
+
+def tlm_close(st):
+    st["m"].close()
+    st["g"].close()
+    st["seq"]["ex"].close() if hasattr(st["seq"]["ex"], "close") else None
+
+
+def test_run_track_chain_equals_the_model_and_the_host_offset_search(torch_dev):
+    """The runner of the stream-order tests: UpdateLocalMap against the model, the search's
+    frame_mp and nmatches against the host-offset entry point on the model's lists, PoseOptimization's
+    edge counts against the searched tables (its arithmetic is test_gpu_pose_opt.py's), and the
+    tally against the model on PoseOptimization's flags."""
+    st = tlm_setup()
+    got = run_track_chain(st)
+    ref = run_track_chain(st, host_offsets=True)
+    want, inp = st["want"], st["inp"]
+    LM.assert_same({k: got[k] for k in ("local_kf", "local_kf_n", "ref_kf", "local_off", "local_ids", "counts", "status")},
+                   want)
+    # the tally rewrites frame_mp: the search's result is what it was before the tally's discards
+    w_fm, w_inl, w_ok, w_found = LM.tally(ref["frame_mp"], inp["n"], got["outlier"], inp["observations"], False, False,
+                                          inp["rec"], inp["found"])
+    assert got["nmatches"].tobytes() == ref["nmatches"].tobytes() and int(got["nmatches"].sum()) > 50 * st["B"]
+    assert np.array_equal(got["frame_mp"], w_fm) and np.array_equal(got["inliers"], w_inl)
+    assert np.array_equal(got["ok"], w_ok) and np.array_equal(got["found"], w_found) and w_inl.max() > 10
+    n_mp = len(inp["pos"])
+    for b in range(st["B"]):
+        have = int(((ref["frame_mp"][b] >= 0) & (ref["frame_mp"][b] < n_mp))[:inp["n"][b]].sum())
+        assert 0 < got["ninliers"][b] <= got["ninit"][b] <= have and np.isfinite(got["Tcw_opt"][b]).all()
+    tlm_close(st)
 
 
 def test_chain_update_local_map_search_local_points_tally(torch_dev):

@@ -460,9 +460,27 @@ def _kf_views(oracle, seed, prm=S.C1):
     return views, has, fvs
 
 
-def _upload_kfs(views, has, fvs, cap, dev):
+def _kf_decoy(name, a):
+    """A keyframe table's decoy: other descriptors, keypoint coordinates and right coordinates;
+    the flags, FeatureVector tables and counts are the real ones."""
+    if name == "de":                       # a mask per row: one mask for all would keep every distance
+        return a ^ ((np.arange(len(a)) * 37 + 11) & 0xFF).astype(np.uint8)[:, None]
+    if name == "kp":
+        d = a.copy()
+        d[:, :2].view(np.float32)[...] += np.float32(3.5)
+        return d
+    if name == "ur":
+        return np.where(a >= 0, a + np.float32(2.0), a).astype(np.float32)
+    return a
+
+
+def _upload_kfs(views, has, fvs, cap, dev, io=None, decoy=False):
+    """io: a stream_order I/O object for the uploads (default: blocking ones); decoy: _kf_decoy's
+    tables are in place until an ordered run's real uploads."""
     import torch
     from orbslam2commentedbyxcm_amd.matcher import keyframe_device
+    up = (lambda k, v: torch.from_numpy(v).to(dev)) if io is None else \
+        (lambda k, v: io.up(v, _kf_decoy(k, v) if decoy else None))
     keep, recs = [], []
     for V, h, (fn, fo, fi) in zip(views, has, fvs):
         n = len(V.keys)
@@ -479,17 +497,56 @@ def _upload_kfs(views, has, fvs, cap, dev):
         off[:len(fo)] = fo
         idx = np.zeros(cap, np.int32)
         idx[:len(fi)] = fi
-        t = {k: torch.from_numpy(v).to(dev) for k, v in
+        t = {k: up(k, v) for k, v in
              dict(kp=kp, de=de, hm=hm, node=node, off=off, idx=idx, n=np.array([n], np.int32),
                   nfv=np.array([len(fn)], np.int32)).items()}
         if V.u_right is not None:
             ur = np.full(cap, -1.0, np.float32)
             ur[:n] = V.u_right
-            t["ur"] = torch.from_numpy(ur).to(dev)
+            t["ur"] = up("ur", ur)
         keep.append(t)
         recs.append(keyframe_device(t["kp"], t["de"], t["n"], t["hm"], t["node"], t["off"], t["idx"], t["nfv"],
                                     V.Tcw, t.get("ur")))
     return keep, recs
+
+
+SFT_KEYS = ("m12", "pairs", "npairs")
+
+
+def run_search_for_triangulation(m, case, io=None, decoy=False, decoy_only=False):
+    """SearchForTriangulationBatchDevice over every ordered pair of case = _kf_views(...): the
+    host tables pairs and F12 go through io.host (their decoys: the pairs reversed, F12
+    transposed).  io: a stream_order I/O object (default: blocking uploads, a device synchronise
+    around the call); decoy: the keyframes' decoy tables are in place before an ordered run's
+    real uploads; decoy_only: run on the decoy tables."""
+    import torch
+
+    import stream_order as SO
+    views, has, fvs = case
+    dev = torch.device("cuda", 0)
+    io = io or SO.SyncIO(dev)
+    cap = max(len(V.keys) for V in views) + 37
+    if decoy_only:
+        class _Decoy(SO.SyncIO):
+            def up(self, real, d=None):
+                return super().up(real if d is None else d)
+        keep, recs = _upload_kfs(views, has, fvs, cap, dev, io=_Decoy(dev), decoy=True)
+    else:
+        keep, recs = _upload_kfs(views, has, fvs, cap, dev, io=io, decoy=decoy)
+    pairs = np.array([(i, j) for i in range(4) for j in range(4) if i != j], np.int32)
+    F12 = np.stack([S.fundamental(views[i], views[j]) for i, j in pairs]).astype(np.float32)
+    P = len(pairs)
+    d_m12 = io.full((P, cap), -9, torch.int32)
+    d_pairs = io.full((P, cap, 2), -9, torch.int32)
+    d_np = io.full((P,), -9, torch.int32)
+    cam = FrameView(keys=views[0].keys[:0], desc=views[0].desc[:0], scale_factors=views[0].scale_factors,
+                    level_sigma2=views[0].level_sigma2)
+    h_pairs = io.host(pairs, np.ascontiguousarray(pairs[:, ::-1]))
+    h_F = io.host(np.ascontiguousarray(F12), np.ascontiguousarray(F12.transpose(0, 2, 1)))
+    io.begin()
+    m.SearchForTriangulationBatchDevice(recs, cam, h_pairs, h_F, cap, d_m12, d_pairs, d_np, stream=io.stream)
+    io.end()
+    return dict(m12=io.down(d_m12), pairs=io.down(d_pairs), npairs=io.down(d_np), keep=keep, F12=F12, host_pairs=pairs)
 
 
 @pytest.mark.parametrize("seed,check_ori,only_stereo,prm", [(0, False, False, S.C1), (1, True, False, S.C1),

@@ -57,31 +57,40 @@ def opt(orbx_built):
 keypoints, pack = M.keypoints, M.pack
 
 
-def run_batch(opt, scenes, trace=True, counts=True):
+def run_batch(opt, scenes, trace=True, counts=True, io=None, decoy=None):
+    """io: a stream_order I/O object (default: blocking uploads, a device synchronise around the
+    call); decoy: the scenes whose arrays fill the inputs before an ordered run's real uploads."""
     import torch
+
+    import stream_order as SO
     P = pack(scenes)
+    Q = P if decoy is None else pack(decoy)
     B, cap1, cap2 = len(scenes), P["cap1"], P["cap2"]
     dev = torch.device("cuda", opt.device)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-    d_m12 = t(P["m12"])
-    d_R = torch.full((B, 9), float("nan"), dtype=torch.float32, device=dev)
-    d_t = torch.full((B, 3), float("nan"), dtype=torch.float32, device=dev)
-    d_s = torch.full((B,), float("nan"), dtype=torch.float32, device=dev)
-    i32 = lambda *shape: torch.full(shape, -9, dtype=torch.int32, device=dev)  # noqa: E731
+    io = io or SO.SyncIO(dev)
+    t = lambda k: io.up(P[k], Q[k])  # noqa: E731
+    kp = lambda k, cap: io.up(P[k].view(np.uint8).reshape(B, cap * 28), Q[k].view(np.uint8).reshape(B, cap * 28))  # noqa: E731
+    d_m12 = t("m12")
+    d_R = io.full((B, 9), float("nan"), torch.float32)
+    d_t = io.full((B, 3), float("nan"), torch.float32)
+    d_s = io.full((B,), float("nan"), torch.float32)
+    i32 = lambda *shape: io.full(shape, -9, torch.int32)  # noqa: E731
     d_nin, d_nc, d_nb = (i32(B), i32(B), i32(B)) if counts else (None, None, None)
     d_tr = i32(B, 2, 2) if trace else None
     s0 = scenes[0]
-    torch.cuda.synchronize(dev)
+    ins = [kp("kps1", cap1), t("n1"), t("mp1"), d_m12, t("idx2"), kp("kps2", cap2), t("n2"), t("pos"), t("Tcw1"), t("Tcw2")]
+    start = [t("R12"), t("t12"), t("s12")]
+    sig1 = io.host(np.asarray(s0["inv_sigma2_1"], np.float32), np.asarray(s0["inv_sigma2_1"], np.float32)[::-1])
+    sig2 = io.host(np.asarray(s0["inv_sigma2_2"], np.float32), np.asarray(s0["inv_sigma2_2"], np.float32)[::-1])
+    K1, K2 = (io.host(np.asarray(s0[k], np.float32), np.asarray(s0[k], np.float32) * np.float32(1.02)) for k in ("K1", "K2"))
+    io.begin()
     opt.optimize_sim3_batch_device(
-        t(P["kps1"].view(np.uint8).reshape(B, cap1 * 28)), t(P["n1"]), t(P["mp1"]), d_m12, t(P["idx2"]),
-        t(P["kps2"].view(np.uint8).reshape(B, cap2 * 28)), t(P["n2"]), t(P["pos"]), t(P["Tcw1"]), t(P["Tcw2"]),
-        s0["inv_sigma2_1"], s0["inv_sigma2_2"], s0["K1"], s0["K2"], t(P["R12"]), t(P["t12"]), t(P["s12"]),
+        *ins, sig1, sig2, K1, K2, *start,
         float(s0["th2"]), s0["fix_scale"], d_R, d_t, d_s, d_ninliers=d_nin, d_ncorr=d_nc, d_nbad=d_nb, d_trace=d_tr,
-        stream=torch.cuda.current_stream(dev))
-    torch.cuda.synchronize(dev)
-    cpu = lambda x: None if x is None else x.cpu().numpy()  # noqa: E731
-    return dict(R12=cpu(d_R), t12=cpu(d_t), s12=cpu(d_s), m12=cpu(d_m12), ninliers=cpu(d_nin), ncorr=cpu(d_nc),
-                nbad=cpu(d_nb), trace=cpu(d_tr), packed=P)
+        stream=io.stream)
+    io.end()
+    return dict(R12=io.down(d_R), t12=io.down(d_t), s12=io.down(d_s), m12=io.down(d_m12), ninliers=io.down(d_nin),
+                ncorr=io.down(d_nc), nbad=io.down(d_nb), trace=io.down(d_tr), packed=P)
 
 
 def s12_of(got, b):

@@ -84,31 +84,40 @@ def pack(scenes):
     return dict(kps=kps, ur=ur if stereo else None, mp=mp, n=n, tcw=tcw, pos=pos, cap=cap, cam=scenes[0]["cam"])
 
 
-def run_batch(opt, scenes, discard=False, mp_obs=None, want_map=False, trace=True, outlier_init=0):
+def run_batch(opt, scenes, discard=False, mp_obs=None, want_map=False, trace=True, outlier_init=0, io=None, decoy=None):
+    """io: a stream_order I/O object (default: blocking uploads, a device synchronise around the
+    call); decoy: the scenes whose arrays fill the inputs before an ordered run's real uploads."""
     import torch
+
+    import stream_order as SO
     P = pack(scenes)
+    Q = P if decoy is None else pack(decoy)
     B, cap = len(scenes), P["cap"]
     dev = torch.device("cuda", opt.device)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-    d_kps = t(P["kps"].view(np.uint8).reshape(B, cap * 28))
-    d_mp = t(P["mp"])
-    d_out = torch.full((B, cap), outlier_init, dtype=torch.uint8, device=dev)
-    d_tout = torch.full((B, 12), float("nan"), dtype=torch.float32, device=dev)
-    d_ninl = torch.full((B,), -9, dtype=torch.int32, device=dev)
-    d_nini = torch.full((B,), -9, dtype=torch.int32, device=dev)
-    d_tr = torch.full((B, 4, 2), -9, dtype=torch.int32, device=dev) if trace else None
-    d_map = torch.full((B,), -9, dtype=torch.int32, device=dev) if want_map else None
+    io = io or SO.SyncIO(dev)
+    t = lambda k: io.up(P[k], Q[k])  # noqa: E731
+    d_kps = io.up(P["kps"].view(np.uint8).reshape(B, cap * 28), Q["kps"].view(np.uint8).reshape(B, cap * 28))
+    d_mp = t("mp")
+    d_out = io.full((B, cap), outlier_init, torch.uint8)
+    d_tout = io.full((B, 12), float("nan"), torch.float32)
+    d_ninl = io.full((B,), -9, torch.int32)
+    d_nini = io.full((B,), -9, torch.int32)
+    d_tr = io.full((B, 4, 2), -9, torch.int32) if trace else None
+    d_map = io.full((B,), -9, torch.int32) if want_map else None
     fx, fy, cx, cy, bf = P["cam"]
-    torch.cuda.synchronize(dev)
+    d_n, d_pos, d_tcw = t("n"), t("pos"), t("tcw")
+    d_ur = None if P["ur"] is None else t("ur")
+    d_obs = None if mp_obs is None else io.up(mp_obs)
+    sig = io.host(np.asarray(M.INV_SIGMA2, np.float32), np.asarray(M.INV_SIGMA2, np.float32)[::-1])
+    io.begin()
     opt.pose_optimization_batch_device(
-        d_kps, t(P["n"]), d_mp, t(P["pos"]), M.INV_SIGMA2, fx, fy, cx, cy, bf, t(P["tcw"]), d_tout, d_out, d_ninl,
-        d_nini, d_u_right=None if P["ur"] is None else t(P["ur"]), d_trace=d_tr, discard_outliers=discard,
-        d_mp_obs=None if mp_obs is None else t(mp_obs), d_nmatches_map=d_map,
-        stream=torch.cuda.current_stream(dev))
-    torch.cuda.synchronize(dev)
-    return dict(Tcw=d_tout.cpu().numpy(), outlier=d_out.cpu().numpy(), ninliers=d_ninl.cpu().numpy(),
-                ninit=d_nini.cpu().numpy(), trace=None if d_tr is None else d_tr.cpu().numpy(),
-                mp=d_mp.cpu().numpy(), nmap=None if d_map is None else d_map.cpu().numpy(), packed=P)
+        d_kps, d_n, d_mp, d_pos, sig, fx, fy, cx, cy, bf, d_tcw, d_tout, d_out, d_ninl,
+        d_nini, d_u_right=d_ur, d_trace=d_tr, discard_outliers=discard,
+        d_mp_obs=d_obs, d_nmatches_map=d_map, stream=io.stream)
+    io.end()
+    return dict(Tcw=io.down(d_tout), outlier=io.down(d_out), ninliers=io.down(d_ninl),
+                ninit=io.down(d_nini), trace=io.down(d_tr),
+                mp=io.down(d_mp), nmap=io.down(d_map), packed=P)
 
 
 def assert_pose_close(got, want32, want64, what):

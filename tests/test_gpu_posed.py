@@ -396,6 +396,65 @@ def test_search_local_points_device(oracle, orbx_built, th, nnratio, footprint, 
     assert total > 100 * B
 
 
+NEW_POINT_KEYS = ("pos", "normal", "max_distance", "min_distance", "observations", "bad", "mp_obs", "mp_pos", "has_mp")
+
+
+def new_point_inputs(seq, seed=41):
+    """Host arrays of create_mappoints_device / update_last_frame_device over the sequence (depths
+    from the scene's plane, a fifth not positive) and their decoy: the same counts and octaves,
+    other keypoint coordinates, depths and poses."""
+    B, cap, n = len(seq["n"]), seq["cap"], seq["n"]
+    rng = np.random.default_rng(seed)
+    depth = np.zeros((B, cap), np.float32)
+    for b in range(B):
+        k = seq["kps"][b][: n[b]]
+        _, z = S.plane_points(seq["rels"][b], k["x"], k["y"])
+        d = z.astype(np.float32)
+        d[rng.random(n[b]) < 0.2] = -1.0
+        depth[b, : n[b]] = d
+    real = dict(kps=np.ascontiguousarray(seq["kps"]).view(np.int32).reshape(B, cap, 7).copy(), n=n.astype(np.int32),
+                T=np.asarray(seq["T"], np.float32), depth=depth)
+    return real, new_point_decoy(real)
+
+
+def new_point_decoy(real):
+    kps = real["kps"].copy()
+    kps[..., :2].view(np.float32)[...] += np.float32(1.75)
+    T = real["T"].copy()
+    T[:, [3, 7, 11]] += np.float32([0.04, -0.02, 0.01])
+    depth = real["depth"]
+    return dict(kps=kps, n=real["n"], T=T, depth=np.where(depth > 0, depth * np.float32(1.25), depth).astype(np.float32))
+
+
+def run_new_points(seq, real, io=None, decoy=None, th_depth=40.0):
+    """create_mappoints_device (per-keypoint depths; its host scale factors through io.host) and
+    update_last_frame_device on io's stream with nothing read back in between.  io: a
+    stream_order I/O object (default: blocking uploads, a device synchronise around the calls);
+    decoy: the arrays in place before an ordered run's real uploads."""
+    import torch
+
+    import stream_order as SO
+    from orbslam2commentedbyxcm_amd.matcher import create_mappoints_device, update_last_frame_device
+    io = io or SO.SyncIO(seq["dev"])
+    B, cap = len(seq["n"]), seq["cap"]
+    N = B * cap
+    d = {k: io.up(real[k], (decoy or real)[k]) for k in real}
+    f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+    tab = {"pos": io.full((N, 3), -7.0, f32), "normal": io.full((N, 3), -7.0, f32), "max_distance": io.full((N,), -7.0, f32),
+           "min_distance": io.full((N,), -7.0, f32), "observations": io.full((N,), -7, i32), "bad": io.full((N,), 7, u8)}
+    last = {"mp_obs": io.full((B, cap), -7, i32), "mp_pos": io.full((B, cap, 3), -7.0, f32), "has_mp": io.full((B, cap), 7, u8)}
+    sf0 = np.asarray(seq["ex"].GetScaleFactors(), np.float32)
+    sf = io.host(sf0, sf0[::-1].copy())
+    io.begin()
+    create_mappoints_device(d["kps"], d["n"], d["T"], sf, S.FX, S.FY, S.CX, S.CY, tab, d_depth=d["depth"], stream=io.stream)
+    io.end()
+    update_last_frame_device(d["kps"], d["n"], d["depth"], d["T"], S.FX, S.FY, S.CX, S.CY, th_depth, last, stream=io.stream)
+    io.end()
+    got = {k: io.down(v) for k, v in tab.items()}
+    got.update({k: io.down(v) for k, v in last.items()})
+    return got
+
+
 def test_create_mappoints_device(oracle, orbx_built):
     """Tracking::CreateNewKeyFrame's MapPoints on the device (UnprojectStereo +
     UpdateNormalAndDepth) == the oracle's, bit for bit, for per-keypoint depths (some not

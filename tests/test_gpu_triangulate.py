@@ -58,38 +58,69 @@ def tri(orbx_built):
 SENT_U8, SENT_F32, SENT_I32 = 0xA5, -12345.5, -77
 
 
-def sentinel_outputs(P, cap, dev, skip=()):
+def sentinel_outputs(P, cap, dev, skip=(), full=None):
     import torch
-    f = lambda *s: torch.full(s, SENT_F32, dtype=torch.float32, device=dev)  # noqa: E731
-    u = lambda *s: torch.full(s, SENT_U8, dtype=torch.uint8, device=dev)  # noqa: E731
-    i = lambda *s: torch.full(s, SENT_I32, dtype=torch.int32, device=dev)  # noqa: E731
+    full = full or (lambda shape, v, dtype: torch.full(shape, v, dtype=dtype, device=dev))
+    f = lambda *s: full(s, SENT_F32, torch.float32)  # noqa: E731
+    u = lambda *s: full(s, SENT_U8, torch.uint8)  # noqa: E731
+    i = lambda *s: full(s, SENT_I32, torch.int32)  # noqa: E731
     out = {"reason": u(P, cap), "method": u(P, cap), "pos": f(P, cap, 3), "normal": f(P, cap, 3),
            "max_distance": f(P, cap), "min_distance": f(P, cap), "nnew": i(P), "new_idx": i(P, cap)}
     return {k: v for k, v in out.items() if k not in skip}
 
 
-def run_batch(tri, sc, rows=None, skip=()):
-    """The batch call on the scene's rows; returns host arrays of the outputs (+ the packed inputs)."""
+def decoy_pack(Pk):
+    """The packed scene with every keyframe's keypoints, right coordinates and depths moved; the
+    pair tables, counts and octaves are the real ones."""
+    Q = dict(Pk)
+    Q["kfs"] = []
+    for K in Pk["kfs"]:
+        D = dict(K)
+        for k in ("keys_un", "keys"):
+            if K[k] is not None:
+                D[k] = K[k].copy()
+                D[k]["x"] += np.float32(1.5)
+                D[k]["y"] -= np.float32(0.75)
+        for k, d in (("u_right", 0.5), ("depth", 0.125)):
+            if K[k] is not None:
+                D[k] = np.where(K[k] > 0, K[k] + np.float32(d), K[k]).astype(np.float32)
+        Q["kfs"].append(D)
+    return Q
+
+
+def run_batch(tri, sc, rows=None, skip=(), io=None, decoy=False, packed=None):
+    """The batch call on the scene's rows; returns host arrays of the outputs (+ the packed inputs).
+    io: a stream_order I/O object (default: blocking uploads, a device synchronise around the
+    call); decoy: fill the inputs with decoy_pack's arrays before an ordered run's real uploads;
+    packed: the packed inputs to run instead of the scene's."""
     import torch
 
+    import stream_order as SO
     from orbslam2commentedbyxcm_amd.mapping import keyframe_geom_device
-    Pk = M.pack(sc, rows)
+    Pk = M.pack(sc, rows) if packed is None else packed
+    Qk = decoy_pack(Pk) if decoy else Pk
     dev = torch.device("cuda", tri.device)
-    t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    io = io or SO.SyncIO(dev)
+    raw = lambda K, k: K[k].view(np.uint8) if k in ("keys_un", "keys") and K[k] is not None else K[k]  # noqa: E731
     keep, recs = [], []
-    for K in Pk["kfs"]:
-        d = {k: t(K[k].view(np.uint8) if k in ("keys_un", "keys") and K[k] is not None else K[k])
-             for k in ("keys_un", "keys", "u_right", "depth", "n")}
+    for K, D in zip(Pk["kfs"], Qk["kfs"]):
+        d = {k: None if K[k] is None else io.up(raw(K, k), raw(D, k)) for k in ("keys_un", "keys", "u_right", "depth", "n")}
         keep.append(d)
         recs.append(keyframe_geom_device(d["keys_un"], d["n"], K["Tcw"].reshape(3, 4), d["u_right"], d["depth"], d["keys"]))
     P, cap = len(Pk["pairs"]), Pk["cap"]
-    out = sentinel_outputs(max(P, 1), cap, dev, skip)
-    d_pairs, d_np = t(Pk["d_pairs"] if P else np.zeros((1, cap, 2), np.int32)), t(Pk["npairs"] if P else np.zeros(1, np.int32))
-    torch.cuda.synchronize(dev)
-    tri.triangulate_pairs_batch_device(recs, M.cam(), Pk["pairs"], cap, d_pairs, d_np, out,
-                                       stream=torch.cuda.current_stream(dev))
-    torch.cuda.synchronize(dev)
-    got = {k: v.cpu().numpy() for k, v in out.items()}
+    out = sentinel_outputs(max(P, 1), cap, dev, skip, io.full)
+    d_pairs = io.up(Pk["d_pairs"] if P else np.zeros((1, cap, 2), np.int32))
+    d_np = io.up(Pk["npairs"] if P else np.zeros(1, np.int32))
+    pairs = np.ascontiguousarray(Pk["pairs"], np.int32).reshape(-1, 2)
+    h_pairs = io.host(pairs, pairs[:, ::-1])
+    cam = M.cam()                                     # its level tables are the caller's host arrays too
+    for name in ("scale_factors", "level_sigma2"):
+        a = np.ascontiguousarray(getattr(cam, name), np.float32)
+        setattr(cam, name, io.host(a, a[::-1].copy()))
+    io.begin()
+    tri.triangulate_pairs_batch_device(recs, cam, h_pairs, cap, d_pairs, d_np, out, stream=io.stream)
+    io.end()
+    got = {k: io.down(v) for k, v in out.items()}
     got["packed"] = Pk
     return got
 
