@@ -271,6 +271,17 @@ typedef struct orbx_matcher orbx_matcher;
 int orbx_matcher_create(int device, float nnratio, int check_ori, orbx_matcher** out);
 void orbx_matcher_destroy(orbx_matcher* m);
 
+/* Size limits of the four single-call SearchByProjection forms below.  The frame whose
+ * keypoints are searched (f, cur, kf) holds at most 8191 keypoints: the sorted grid encodes
+ * a keypoint's position in 13 bits.  n >= 8192 returns ORBX_ERR_UNSUPPORTED, decided before
+ * anything is uploaded or launched; the caller's arrays are untouched.  The number of
+ * queries (nq, the last frame's or keyframe's keypoints, npoints) is bounded only by
+ * memory: queries are not position-encoded, and every nq works with every n <= 8191.
+ * The searched frame's nlevels is 1..32 for the first two forms (F, CurrentFrame against
+ * LastFrame) and 2..32 for the KeyFrame and Sim3 forms, whose PredictScale needs
+ * scale_factors[1]; anything else is ORBX_ERR_ARG, checked on entry before the level tables
+ * are read.  Every keypoint octave is below nlevels; the frame's top levels may be empty. */
+
 /* SearchByProjection(Frame& F, const vector<MapPoint*>& vpMapPoints, const float th)
  * ORBmatcher.cc:61-173.  frame_mp (F.mvpMapPoints as MapPoint ids, -1 = NULL) is
  * updated in place; queries = vpMapPoints ids in order. */
@@ -325,7 +336,13 @@ int orbx_match_sequence_device(orbx_matcher* m, int batch, const orbx_keypoint* 
  * (bForward / bBackward, cc:1650-1701) and the mvuRight check (cc:1722-1729).
  * LastFrame keypoint i's MapPoint (id i, Observations() > 0) sits at mp_pos
  * (LastFrame.mvpMapPoints[i]->GetWorldPos()) or, without mp_pos, at `depth` on its
- * viewing ray; has_mp clears keypoints with no MapPoint or flagged mvbOutlier. */
+ * viewing ray; has_mp clears keypoints with no MapPoint or flagged mvbOutlier.
+ * Both sequence forms: where no LDS layout of the matcher's footprint
+ * (orbx_matcher_set_footprint) holds cap keypoints x nlevels octave buckets -- at 8 levels
+ * cap >= 6730 in footprints 0, 1, 3, 4; at 32 levels cap >= 2661 in every footprint but 2;
+ * cap >= 8192 in footprints 0, 1, 3, 4, 5 -- the call returns ORBX_ERR_UNSUPPORTED before
+ * anything is launched, the outputs untouched.  Footprint 2 (the split launches) holds
+ * every cap below 8192 at every nlevels. */
 typedef struct {
     int batch;                    /* B frames */
     const orbx_keypoint* kps;     /* [B][cap] mvKeysUn (device) */
@@ -369,8 +386,12 @@ int orbx_match_sequence_device_ex(orbx_matcher* m, const orbx_sequence* seq, voi
  *      order: frame_mp is updated in place, nmatches [b] receives its count.
  * MapPoints live in a device table indexed by id.  local_off is a host array (B + 1
  * ints: it sizes the launch); every other pointer is a device pointer.  cap must stay
- * below 8192 (keypoints); a local map may hold up to 2^20 MapPoints.  Asynchronous on
- * `stream` (or the matcher's). */
+ * below 8192 (keypoints); a local map may hold up to 2^20 MapPoints.  Where no LDS layout
+ * of the matcher's footprint holds cap keypoints x the largest local map x nlevels (the
+ * limits of orbx_match_sequence_device_ex; a larger local map only moves the query state
+ * out of LDS), the call returns ORBX_ERR_UNSUPPORTED before anything is launched, frame_mp
+ * and nmatches untouched; footprint 2 holds every valid size.  Asynchronous on `stream` (or
+ * the matcher's). */
 typedef struct {
     int n;                        /* MapPoints in the table */
     const float* pos;             /* [n][3] GetWorldPos() */

@@ -99,6 +99,11 @@ public:
 
     static int DescriptorDistance(const uint8_t* a, const uint8_t* b) { return orbx_hamming(a, b); }
 
+    // The four SearchByProjection overloads: the searched frame (F, CurrentFrame, KF) holds at
+    // most 8191 keypoints -- 8192 or more throws before anything is uploaded
+    // (ORBX_ERR_UNSUPPORTED), the caller's arrays untouched; the number of queries
+    // (vpMapPoints, the last frame's / keyframe's keypoints, vpPoints) is bounded only by memory.
+
     // SearchByProjection(Frame&, const vector<MapPoint*>&, th)
     int SearchByProjection(const orbx_frame_view& F, int32_t* mvpMapPoints, const std::vector<int32_t>& vpMapPoints,
                            const orbx_mappoints& mps, const orbx_track& trk, float th = 3) {

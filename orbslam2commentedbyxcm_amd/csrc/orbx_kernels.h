@@ -76,10 +76,24 @@ hipError_t launch_extract(const Plan& plan, const DeviceBuffers& db, int batch, 
 hipError_t launch_hamming_matrix(const uint8_t* a, int na, const uint8_t* b, int nb, int32_t* dist,
                                  hipStream_t stream);
 
+// The k_proj_search instantiation launch_proj_search chose (diagnostics; host memory):
+// query state / descriptors in LDS, the workgroup's threads, its dynamic LDS bytes.
+struct ProjForm {
+    int qlds, dlds, threads;
+    size_t lds;
+};
+
+// The form launch_proj_search would run for these sizes: hipErrorInvalidValue where none
+// fits the 160 KB of LDS (or max_n >= 8192, noct outside 1..32).  Host arithmetic only, so
+// a caller can refuse before its first launch.  split: with split_grids.
+hipError_t proj_search_form(int max_n, int max_nq, int noct, bool small, bool tiny, bool lean, bool split,
+                            ProjForm* form);
+
+// form (nullable): the form chosen.  Refuses as proj_search_form does, launching nothing.
 hipError_t launch_proj_search(const ProjProblem* d_probs, int nprob, const ProjParams& P, unsigned long long* scratch,
                               const long long* d_scratch_off, int max_n, int max_nq, hipStream_t stream,
                               bool small = false, bool tiny = false, bool lean = false,
-                              unsigned char* split_grids = nullptr);
+                              unsigned char* split_grids = nullptr, ProjForm* form = nullptr);
 
 // k_seq_grid + k_seq_score + k_seq_commit: the split form of launch_proj_search for the
 // batched sequence matcher (grids: nprob x seq_grid_bytes(cap) bytes of device memory).

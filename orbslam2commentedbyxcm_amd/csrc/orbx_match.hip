@@ -2225,12 +2225,10 @@ hipError_t launch_seq_build(const SeqArgs& A, int npairs, ProjQuery* queries, Pr
     return hipGetLastError();
 }
 
-hipError_t launch_proj_search(const ProjProblem* d_probs, int nprob, const ProjParams& P, unsigned long long* scratch,
-                              const long long* d_scratch_off, int max_n, int max_nq, hipStream_t stream, bool small,
-                              bool tiny, bool lean, unsigned char* split_grids) {
-    if (nprob <= 0) return hipSuccess;
+hipError_t proj_search_form(int max_n, int max_nq, int noct, bool small, bool tiny, bool lean, bool split,
+                            ProjForm* form) {
     if (max_n >= 8192) return hipErrorInvalidValue;  // 13-bit keypoint positions
-    if (P.noct < 1 || P.noct > 32) return hipErrorInvalidValue;
+    if (noct < 1 || noct > 32) return hipErrorInvalidValue;
     const size_t limit = 160 * 1024 - 256;  // minus the static histogram
     // Fast: LDS-resident descriptors (the scoring loads), then LDS-resident query state,
     // 1024 threads.  Small (meant to run beside other kernels): neither, 256 threads.
@@ -2238,21 +2236,37 @@ hipError_t launch_proj_search(const ProjProblem* d_probs, int nprob, const ProjP
     // lean: 1024 threads, but only the grid and the claims in LDS (descriptors and query
     // state in global memory) -- the form that shares a CU best with other kernels
     bool dlds = !small && !lean, qlds = !small && !lean;
-    if (dlds && ProjLds(max_n, max_nq, true, true, P.noct).total > limit) {
+    if (dlds && ProjLds(max_n, max_nq, true, true, noct).total > limit) {
         qlds = false;
-        if (ProjLds(max_n, max_nq, true, false, P.noct).total > limit) {
+        if (ProjLds(max_n, max_nq, true, false, noct).total > limit) {
             dlds = false;
-            qlds = ProjLds(max_n, max_nq, false, true, P.noct).total <= limit;
+            qlds = ProjLds(max_n, max_nq, false, true, noct).total <= limit;
         }
     }
-    if (split_grids) {  // lean scoring kernel + k_seq_commit
+    if (split) {  // lean scoring kernel + k_seq_commit
         if (small) return hipErrorInvalidValue;
         dlds = qlds = false;
     }
-    const size_t lds = ProjLds(max_n, max_nq, dlds, qlds, P.noct, split_grids == nullptr).total;
+    const size_t lds = ProjLds(max_n, max_nq, dlds, qlds, noct, !split).total;
     if (lds > limit) return hipErrorInvalidValue;
+    const int nt = tiny ? kProjThreadsTiny : (small ? kProjThreadsSmall : (split ? kSplitScoreThreads : kProjThreads));
+    *form = ProjForm{qlds ? 1 : 0, dlds ? 1 : 0, nt, lds};
+    return hipSuccess;
+}
+
+hipError_t launch_proj_search(const ProjProblem* d_probs, int nprob, const ProjParams& P, unsigned long long* scratch,
+                              const long long* d_scratch_off, int max_n, int max_nq, hipStream_t stream, bool small,
+                              bool tiny, bool lean, unsigned char* split_grids, ProjForm* form) {
+    if (nprob <= 0) return hipSuccess;
+    ProjForm f{};
+    const hipError_t fe = proj_search_form(max_n, max_nq, P.noct, small, tiny, lean, split_grids != nullptr, &f);
+    if (fe != hipSuccess) return fe;
+    if (form) *form = f;
+    small = small || tiny;
+    const bool dlds = f.dlds != 0, qlds = f.qlds != 0;
+    const size_t lds = f.lds;
+    const int nt = f.threads;
     const void* fn;
-    const int nt = tiny ? kProjThreadsTiny : (small ? kProjThreadsSmall : (split_grids ? kSplitScoreThreads : kProjThreads));
     if (tiny)
         fn = (const void*)k_proj_search<false, false, kProjThreadsTiny>;
     else if (small)

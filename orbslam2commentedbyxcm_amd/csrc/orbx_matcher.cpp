@@ -242,19 +242,25 @@ int run_proj(orbx_matcher* m, const orbx_frame_view* f, int32_t* frame_mp, const
         return ORBX_OK;
     }
     if (mps->n < 0 || mps->n >= kMaxMapPointIds) return fail(ORBX_ERR_ARG, "MapPoint table of 2^30 or more");
+    // the sorted grid encodes a keypoint's position in 13 bits; the queries are not
+    // position-encoded, so their number is bounded only by memory
+    if (n >= 8192) return fail(ORBX_ERR_UNSUPPORTED, "SearchByProjection: 8192 or more keypoints in the frame (limit 8191)");
     const auto t_stage0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(m->device));
     const int nobs = mps->n;
     size_t need = pad(sizeof(orbx_keypoint) * n) + pad((size_t)n * 32) + pad(sizeof(float) * n) +
                   pad(sizeof(int32_t) * n) + pad(sizeof(ProjQuery) * nq) + pad((size_t)nq * 32) +
                   pad(sizeof(int32_t) * (nobs ? nobs : 1)) + pad(sizeof(ProjProblem)) + pad(8 * kProjScratchWords * (size_t)nq) +
-                  pad(sizeof(long long)) + pad(sizeof(int32_t));
+                  pad(sizeof(long long));
     // one problem: the split launches (grid sort, scoring spread over nq / 16 workgroups,
-    // one-wave commit) finish sooner than one workgroup doing all three
-    const int gcap = n > nq ? n : nq;
-    // octave buckets of the device grid: one per octave present (the grid keys hold
-    // octave & 31)
-    int noct = 1;
+    // one-wave commit) finish sooner than one workgroup doing all three.  The grid holds the
+    // frame's n keypoints; the scoring launch is sized by the nq queries.
+    const int gcap = n;
+    // octave buckets of the device grid: one per level of the frame, and per octave present
+    // (the grid keys hold octave & 31).  The scoring clamps a query's octave range onto the
+    // buckets, so a range must never lie wholly above them: every range the overloads build
+    // starts below nlevels, but may start above the highest octave that has a keypoint.
+    int noct = f->nlevels;
     for (int i = 0; i < n; i++) {
         const int o = f->keys[i].octave & 31;
         if (o + 1 > noct) noct = o + 1;
@@ -271,7 +277,6 @@ int run_proj(orbx_matcher* m, const orbx_frame_view* f, int32_t* frame_mp, const
     auto* d_obs = m->arena.take<int32_t>(nobs ? nobs : 1);
     auto* d_prob = m->arena.take<ProjProblem>(1);
     auto* d_off = m->arena.take<long long>(1);
-    auto* d_nm = m->arena.take<int32_t>(1);
     // device-only areas last: the staged (uploaded) prefix ends before them
     auto* d_scr = m->arena.take<unsigned long long>(kProjScratchWords * (size_t)nq);
     auto* d_grid = m->arena.take<unsigned char>(seq_grid_bytes(gcap, noct));
@@ -297,9 +302,7 @@ int run_proj(orbx_matcher* m, const orbx_frame_view* f, int32_t* frame_mp, const
     pb.min_y = f->min_y;
     pb.inv_w = (float)kGridCols / (f->max_x - f->min_x);  // Frame.cc:157-159
     pb.inv_h = (float)kGridRows / (f->max_y - f->min_y);
-    pb.nmatches = d_nm;
     const long long zero = 0;
-    m->arena.up(d_prob, &pb, sizeof(pb));
     m->arena.up(d_off, &zero, sizeof(zero));
     ProjParams P = base_params;
     P.mp_obs = d_obs;
@@ -315,8 +318,7 @@ int run_proj(orbx_matcher* m, const orbx_frame_view* f, int32_t* frame_mp, const
         P.stamps = d_st;
     }
     // results straight into host-mapped memory (k_seq_commit's out_mp and the count)
-    const bool mapped = gcap < 8192;
-    if (mapped && m->hmp_cap < (size_t)n + 1) {
+    if (m->hmp_cap < (size_t)n + 1) {
         HIP_TRY(hipStreamSynchronize(s));
         if (m->hmp) (void)hipHostFree(m->hmp);
         m->hmp = m->hmp_dev = nullptr;
@@ -328,35 +330,21 @@ int run_proj(orbx_matcher* m, const orbx_frame_view* f, int32_t* frame_mp, const
         HIP_TRY(hipHostGetDevicePointer((void**)&m->hmp_dev, m->hmp, 0));
         m->hmp_cap = (size_t)n + 1;
     }
-    if (mapped) {
-        P.out_mp = m->hmp_dev + 1;
-        pb.nmatches = m->hmp_dev;
-        m->arena.up(d_prob, &pb, sizeof(pb));
-    }
-    if (mapped) {
-        // inputs copied in by k_stage_copy (no DMA), results written to mapped memory
-        const size_t staged = m->arena.take_staged();
-        // replay width: the row's (replay_rt) unless switch replay_threads overrides it
-        const bool rt_env = tuning(Tune::ReplayThreads, 0) > 0;
-        HIP_TRY(launch_seq_split(d_prob, 1, P, d_grid, gcap, d_scr, d_off, s, 0, rt_env ? 0 : replay_rt,
-                                 m->arena.host_dev, m->arena.base, staged));
-    } else {
-        HIP_TRY(m->arena.flush(s));
-        HIP_TRY(launch_proj_search(d_prob, 1, P, d_scr, d_off, n, nq, s));
-    }
+    P.out_mp = m->hmp_dev + 1;
+    pb.nmatches = m->hmp_dev;
+    m->arena.up(d_prob, &pb, sizeof(pb));
+    // inputs copied in by k_stage_copy (no DMA), results written to mapped memory
+    const size_t staged = m->arena.take_staged();
+    // replay width: the row's (replay_rt) unless switch replay_threads overrides it
+    const bool rt_env = tuning(Tune::ReplayThreads, 0) > 0;
+    HIP_TRY(launch_seq_split(d_prob, 1, P, d_grid, gcap, d_scr, d_off, s, nq, rt_env ? 0 : replay_rt,
+                             m->arena.host_dev, m->arena.base, staged));
     // the caller's frame_mp is written only once the count says the replay converged: a
     // failed call (ORBX_ERR_STATE below) leaves it as it was
-    int nm = 0;
-    std::vector<int32_t> staged_mp;
-    if (!mapped) {
-        staged_mp.resize((size_t)n);
-        HIP_TRY(m->arena.down(staged_mp.data(), d_fmp, sizeof(int32_t) * n, s));
-        HIP_TRY(m->arena.down(&nm, d_nm, sizeof(int32_t), s));
-    }
     const auto t_enq = std::chrono::steady_clock::now();
     HIP_TRY(m->arena.sync(s));
-    if (mapped) nm = m->hmp[0];
-    if (nm >= 0) std::memcpy(frame_mp, mapped ? m->hmp + 1 : staged_mp.data(), sizeof(int32_t) * n);
+    const int nm = m->hmp[0];
+    if (nm >= 0) std::memcpy(frame_mp, m->hmp + 1, sizeof(int32_t) * n);
     if (call_stamps) {
         const auto t_done = std::chrono::steady_clock::now();
         unsigned long long h[kStampWords];
@@ -365,11 +353,12 @@ int run_proj(orbx_matcher* m, const orbx_frame_view* f, int32_t* frame_mp, const
         auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
         fprintf(stderr, "[orbx call] n=%d nq=%d | host staging %.1f us, enqueue %.1f us, wait %.1f us | grid: start %.1f, "
                 "sort %.1f, writes %.1f, colstart %.1f, runs %.1f us | replay (%llu threads) %.1f us, %llu iterations, "
-                "%llu re-scored (%.1f us), ",
+                "%llu re-scored%s (%.1f us), ",
                 n, nq, us(t_stage0, t_flush), us(t_flush, t_enq), us(t_enq, t_done), (double)(h[1] - h[0]) * 0.01,
                 (double)(h[2] - h[1]) * 0.01, (double)(h[4] - h[2]) * 0.01, (double)(h[10] - h[4]) * 0.01,
                 (double)(h[11] - h[10]) * 0.01, h[kStampForm], (double)(h[3] - h[13]) * 0.01, h[7], h[5],
-                (double)h[8] * 0.01);
+                // the workgroup replays count per wave and thread 0 reports its own wave's
+                h[kStampForm] == 64 ? "" : " by the first wave", (double)h[8] * 0.01);
         if (h[kStampForm] == 64)  // one wave: 9 = loads + first rounds (cumulative), 15 = a clock reading
             fprintf(stderr, "chunk loads %.1f + first rounds %.1f us, after the loop %.1f us\n", (double)h[14] * 0.01,
                     h[9] >= h[14] ? (double)(h[9] - h[14]) * 0.01 : 0.0,
@@ -428,6 +417,7 @@ int orbx_search_by_projection_local(orbx_matcher* m, const orbx_frame_view* f, i
                                     float th, int* nmatches) {
     const CallClock clock_(m);
     if (!m || !f || !frame_mp || !mps || !trk || (nq && !queries)) return fail(ORBX_ERR_ARG, "null argument");
+    if (f->nlevels < 1 || f->nlevels > 32) return fail(ORBX_ERR_ARG, "nlevels must be 1 .. 32");
     const bool bFactor = th != 1.0;  // ORBmatcher.cc:66
     std::vector<ProjQuery> qs;
     std::vector<uint8_t> qd;
@@ -472,6 +462,7 @@ int orbx_search_by_projection_frame(orbx_matcher* m, const orbx_frame_view* cur,
                                     const orbx_mappoints* mps, float th, int mono, int* nmatches) {
     const CallClock clock_(m);
     if (!m || !cur || !cur_mp || !last || !last_mp || !mps || !mps->pos) return fail(ORBX_ERR_ARG, "null argument");
+    if (cur->nlevels < 1 || cur->nlevels > 32) return fail(ORBX_ERR_ARG, "nlevels must be 1 .. 32");
     float twc[3], tlc[3];
     centre(cur->Tcw, twc);       // twc = -Rcw^T tcw (cc:1637)
     project(last->Tcw, twc, tlc);  // tlc = Rlw*twc + tlw (cc:1643)
@@ -537,7 +528,7 @@ int orbx_search_by_projection_keyframe(orbx_matcher* m, const orbx_frame_view* c
     const CallClock clock_(m);
     if (!m || !cur || !cur_mp || !kf || !kf_mp || !mps || !mps->pos || !mps->max_distance || !mps->min_distance)
         return fail(ORBX_ERR_ARG, "null argument");
-    if (cur->nlevels < 2) return fail(ORBX_ERR_ARG, "need >= 2 pyramid levels");
+    if (cur->nlevels < 2 || cur->nlevels > 32) return fail(ORBX_ERR_ARG, "nlevels must be 2 .. 32");
     float Ow[3];
     centre(cur->Tcw, Ow);  // cc:1796-1798
     std::vector<ProjQuery> qs;
@@ -595,7 +586,7 @@ int orbx_search_by_projection_sim3(orbx_matcher* m, const orbx_frame_view* kf, c
     if (!m || !kf || !Scw || !matched || !mps || !mps->pos || !mps->max_distance || !mps->min_distance ||
         !mps->normal || (npoints && !points))
         return fail(ORBX_ERR_ARG, "null argument");
-    if (kf->nlevels < 2) return fail(ORBX_ERR_ARG, "need >= 2 pyramid levels");
+    if (kf->nlevels < 2 || kf->nlevels > 32) return fail(ORBX_ERR_ARG, "nlevels must be 2 .. 32");
     double d0 = 0.0;
     for (int c = 0; c < 3; c++) d0 += (double)Scw[c] * Scw[c];
     const float scw = (float)std::sqrt(d0);                 // cc:408
@@ -706,6 +697,14 @@ int orbx_match_sequence_device_ex(orbx_matcher* m, const orbx_sequence* sq, void
     const int npairs = batch - 1;
     const bool split = m->footprint == 2;
     const bool grids = split || m->footprint == 5;  // a global grid area per problem
+    // refused before the first launch where no LDS layout fits (the launcher would refuse
+    // only after k_seq_build had written the outputs)
+    ProjForm fits{};
+    if (!split && batch > 1 &&
+        proj_search_form(cap, cap, nlevels, m->footprint == 1, m->footprint == 3, m->footprint == 4, m->footprint == 5,
+                         &fits) != hipSuccess)
+        return fail(ORBX_ERR_UNSUPPORTED, cap >= 8192 ? "cap of 8192 or more keypoints per frame"
+                                                      : "no LDS layout of this footprint holds cap x nlevels");
     const size_t np1 = (size_t)(npairs > 0 ? npairs : 1);
     const size_t need = pad(sizeof(ProjQuery) * np1 * cap) + pad(sizeof(ProjProblem) * np1) +
                         pad(sizeof(long long) * np1) + pad(sizeof(unsigned long long) * kProjScratchWords * np1 * cap) +
@@ -777,11 +776,13 @@ int orbx_match_sequence_device_ex(orbx_matcher* m, const orbx_sequence* sq, void
         HIP_TRY(hipMemsetAsync(d_st, 0, sizeof(unsigned long long) * kStampWords * npairs, s));
         P.stamps = d_st;
     }
+    ProjForm form{};  // what launch_proj_search chose, for the stamps' line
     if (split) {
         HIP_TRY(launch_seq_split(d_prob, npairs, P, d_grids, cap, d_scr, d_off, s));
     } else {
         HIP_TRY(launch_proj_search(d_prob, npairs, P, d_scr, d_off, cap, cap, s, m->footprint == 1,
-                                   m->footprint == 3, m->footprint == 4, m->footprint == 5 ? d_grids : nullptr));
+                                   m->footprint == 3, m->footprint == 4, m->footprint == 5 ? d_grids : nullptr,
+                                   &form));
     }
     if (sq->retry_below > 0) {
         // Tracking::TrackWithMotionModel (Tracking.cc:988-994): pairs left with fewer than
@@ -805,6 +806,10 @@ int orbx_match_sequence_device_ex(orbx_matcher* m, const orbx_sequence* sq, void
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipMemcpy(h.data(), d_st, h.size() * 8, hipMemcpyDeviceToHost));
         HIP_TRY(hipFree(d_st));
+        char formtxt[160] = "";  // the split launches run no k_proj_search: nothing to report
+        if (!split)
+            snprintf(formtxt, sizeof(formtxt), " | form cap=%d max_nq=%d nlevels=%d footprint=%d QLDS=%d DLDS=%d threads=%d lds=%zu",
+                     cap, cap, nlevels, m->footprint, form.qlds, form.dlds, form.threads, form.lds);
         if (grids) {
             double cm = 0, cmx = 0, resc = 0, nq = 0, nit = 0, itmx = 0, sc = 0, gr = 0;
             double tl = 0, tr = 0, tcm = 0, trs = 0, nst = 0;
@@ -852,9 +857,9 @@ int orbx_match_sequence_device_ex(orbx_matcher* m, const orbx_sequence* sq, void
             fprintf(stderr,
                     "[orbx seq stamps] pairs=%d | grid %.1f, scoring %.1f us | commit mean/max %.1f/%.1f us | %.1f "
                     "queries, %.1f re-scored, replay iterations mean/max %.1f/%.0f | chunk loads %.1f, rounds %.1f, "
-                    "commits %.1f, re-scoring %.1f us, %.1f stops\n",
+                    "commits %.1f, re-scoring %.1f us, %.1f stops%s\n",
                     npairs, gr / npairs, sc / npairs, cm / npairs, cmx, nq / npairs, resc / npairs, nit / npairs, itmx,
-                    tl / npairs, tr / npairs, tcm / npairs, trs / npairs, nst / npairs);
+                    tl / npairs, tr / npairs, tcm / npairs, trs / npairs, nst / npairs, formtxt);
             return ORBX_OK;
         }
         double ph[4] = {0, 0, 0, 0}, mx[4] = {0, 0, 0, 0}, resc = 0, nq = 0, nit = 0, tres = 0, tfirst = 0;
@@ -883,10 +888,10 @@ int orbx_match_sequence_device_ex(orbx_matcher* m, const orbx_sequence* sq, void
                 "[orbx stamps] pairs=%d span=%.1fus | mean/max us: sort %.1f/%.1f score %.1f/%.1f commit %.1f/%.1f "
                 "store %.1f/%.1f | rescored %.1f of %.1f queries (%.1f us), %.1f replay rounds (chunk loads + first "
                 "rounds %.1f us) | sort = grid counting sort %.1f + column starts %.1f + octave runs and fill %.1f us | re-scored at a "
-                "truncation %.1f\n",
+                "truncation %.1f%s\n",
                 npairs, (double)(t1 - t0) * 0.01, ph[0] / npairs, mx[0], ph[1] / npairs, mx[1], ph[2] / npairs, mx[2],
                 ph[3] / npairs, mx[3], resc / npairs, nq / npairs, tres / npairs, nit / npairs, tfirst / npairs,
-                tbit / npairs, tfill / npairs, tbuild / npairs, rtrunc / npairs);
+                tbit / npairs, tfill / npairs, tbuild / npairs, rtrunc / npairs, formtxt);
     }
     return ORBX_OK;
 }
@@ -957,6 +962,12 @@ int search_local_points(orbx_matcher* m, const orbx_mappoints_device* mps, const
     hipStream_t s = stream ? (hipStream_t)stream : m->stream;
     const bool split = m->footprint == 2;
     const bool grids = split || m->footprint == 5;
+    // refused before the first launch where no LDS layout fits (the launcher would refuse
+    // only after k_local_build had run)
+    ProjForm fits{};
+    if (!split && proj_search_form(cap, maxnq, nlevels, m->footprint == 1, m->footprint == 3, m->footprint == 4,
+                                   m->footprint == 5, &fits) != hipSuccess)
+        return fail(ORBX_ERR_UNSUPPORTED, "no LDS layout of this footprint holds cap x max local points x nlevels");
     const size_t nt = (size_t)(total > 0 ? total : 1);
     Layout L(pad);
     const size_t o_q = L.take(sizeof(ProjQuery) * nt), o_qd = L.take(nt * 32), o_prob = L.take(sizeof(ProjProblem) * B),
@@ -1025,11 +1036,17 @@ int search_local_points(orbx_matcher* m, const orbx_mappoints_device* mps, const
     P.nnratio = m->nnratio;
     P.check_ori = 0;
     P.noct = nlevels;
-    if (split)
+    if (split) {
         HIP_TRY(launch_seq_split(d_prob, B, P, d_grids, cap, d_scr, d_off, s, maxnq > 0 ? maxnq : 1));
-    else
-        HIP_TRY(launch_proj_search(d_prob, B, P, d_scr, d_off, cap, maxnq, s, m->footprint == 1, m->footprint == 3,
-                                   m->footprint == 4, m->footprint == 5 ? d_grids : nullptr));
+        return ORBX_OK;
+    }
+    ProjForm form{};  // what launch_proj_search chose
+    HIP_TRY(launch_proj_search(d_prob, B, P, d_scr, d_off, cap, maxnq, s, m->footprint == 1, m->footprint == 3,
+                               m->footprint == 4, m->footprint == 5 ? d_grids : nullptr, &form));
+    // switch match_stamps = 1: which form ran, to stderr (diagnostics only; nothing synchronises)
+    if (tuning(Tune::MatchStamps, 0) > 0)
+        fprintf(stderr, "[orbx local stamps] frames=%d | form cap=%d max_nq=%d nlevels=%d footprint=%d QLDS=%d DLDS=%d threads=%d lds=%zu\n",
+                B, cap, maxnq, nlevels, m->footprint, form.qlds, form.dlds, form.threads, form.lds);
     return ORBX_OK;
 }
 
