@@ -571,7 +571,10 @@ int orbx_search_for_triangulation_batch_device(orbx_matcher* m, int nkf, const o
  * mDescriptorsRight.  maxD = mbf / minZ (this fork reads mb before it is set,
  * Frame.cc:711-713; upstream's value is fx).  Writes mvuRight and mvDepth (n_left floats
  * each, -1 = no match), including this fork's in-loop outlier pass (Frame.cc:868-884).
- * Host buffers; synchronous. */
+ * Host buffers; synchronous.  At most 8192 keypoints per image, and the row index of a
+ * pair must fit 150 KB of LDS: ((nlevels + 1) * rows + 2) * 4 <= 153600 bytes (8 levels:
+ * 4266 rows; 12 levels: 2953 rows).  Beyond either limit both forms return
+ * ORBX_ERR_UNSUPPORTED before any upload or launch (this form's outputs are all -1). */
 int orbx_compute_stereo_matches(orbx_matcher* m, orbx_extractor* ex_left, int left_frame, orbx_extractor* ex_right,
                                 int right_frame, const orbx_frame_view* left, const orbx_keypoint* keys_r,
                                 const uint8_t* desc_r, int n_right, float max_disparity, float* u_right,

@@ -122,6 +122,9 @@ hipError_t launch_triangulation(const TriProblem* d_probs, int nprob, unsigned l
 hipError_t launch_triangulation_batch(const TriBatch& tb, unsigned long long* scratch, hipStream_t stream);
 
 hipError_t launch_stereo(const StereoBatch& sb, int batch, hipStream_t stream);
+// k_stereo_index keeps the (octave, row) counters and the row coverage of one pair in LDS
+constexpr size_t kStereoIndexLdsMax = 150 * 1024;
+inline size_t stereo_index_lds(int nlevels, int rows) { return ((size_t)nlevels * rows + 1 + rows + 1) * 4; }
 hipError_t launch_bow(const BowProblem* d_prob, int n2, int nitems, hipStream_t stream);
 hipError_t launch_init(const InitProblem* d_prob, int n1, int n2, int nq, hipStream_t stream);
 hipError_t launch_window_best(const BestProblem* d_prob, int nq, hipStream_t stream);

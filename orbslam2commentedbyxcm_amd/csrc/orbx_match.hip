@@ -3048,8 +3048,8 @@ size_t stereo_outlier_lds(int cap) {
 hipError_t launch_stereo(const StereoBatch& sb, int batch, hipStream_t stream) {
     if (batch <= 0) return hipSuccess;
     if (sb.cap > kSortMaxKeys || sb.rows <= 0 || sb.nlevels < 1 || sb.nlevels > 32) return hipErrorInvalidValue;
-    const size_t idx_lds = ((size_t)sb.nlevels * sb.rows + 1 + sb.rows + 1) * 4;
-    if (idx_lds > 150 * 1024) return hipErrorInvalidValue;
+    const size_t idx_lds = stereo_index_lds(sb.nlevels, sb.rows);
+    if (idx_lds > kStereoIndexLdsMax) return hipErrorInvalidValue;  // the entry points refuse it first
     if (idx_lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)k_stereo_index, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)idx_lds);

@@ -1871,6 +1871,8 @@ int stereo_levels(orbx_extractor* ex_l, orbx_extractor* ex_r, StereoBatch& sb, P
         if (vl.scale[l] != vr.scale[l] || vl.off[l] != vr.off[l] || vl.pitch[l] != vr.pitch[l])
             return fail(ORBX_ERR_ARG, "left and right extractors differ in their scale pyramid");
     sb.rows = vl.h[0];  // mpORBextractorLeft->mvImagePyramid[0].rows (cc:682)
+    if (stereo_index_lds(vl.L, sb.rows) > kStereoIndexLdsMax)
+        return fail(ORBX_ERR_UNSUPPORTED, "stereo row index: (nlevels + 1) * rows + 2 words exceed 150 KB of LDS");
     for (int l = 0; l < vl.L; l++) {
         sb.level_off[l] = vl.off[l];
         sb.level_pitch[l] = vl.pitch[l];
